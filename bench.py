@@ -5,6 +5,7 @@
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # no launcher: bench.py starts its N ranks itself
     python bench.py --config llama-7b   # BASELINE.json configs[4] (opt-1.3b: configs[3])
+    python bench.py --only --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU; it
 starts N child rank processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, as
@@ -255,9 +256,32 @@ def build_block(tuning, dev):
     return block.to(dev)
 
 
-def model_record(tuning, args, world, rank, dev, gemm_timer=None):
+DUMP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, tuner, loss):
+    """--dump-outputs: what the last timed `training_step` gave its caller -- the returned loss,
+    the clip norm it applied and the trainable parameters it updated (tuner.params order, one
+    flat float32 array; past the byte budget a fixed, seeded sample of it)."""
+    os.makedirs(path, exist_ok=True)
+    out = {'loss': loss.detach().float().reshape(1).cpu().numpy()}
+    if tuner.last_grad_norm is not None:
+        out['grad_norm'] = tuner.last_grad_norm.detach().float().reshape(1).cpu().numpy()
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1).float() for p in tuner.params]).cpu().numpy()
+    cap = (DUMP_BYTES - 4096) // 4
+    if flat.size > cap:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, cap, replace=False))]
+    out['trainable_params'] = flat
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return sorted(out)
+
+
+def model_record(tuning, args, world, rank, dev, gemm_timer=None, dump=None):
     """`SparseTuner.training_step` of the 24-layer model; at world > 1 the tuner broadcasts
-    rank 0's replica and all-reduces the trainable gradients inside every step."""
+    rank 0's replica and all-reduces the trainable gradients inside every step.  `dump`: a
+    directory that receives rank 0's outputs of the last timed step (`dump_outputs`)."""
     from naive_gpt import utils
     if not CPU_REHEARSAL:
         torch.cuda.empty_cache()
@@ -271,11 +295,12 @@ def model_record(tuning, args, world, rank, dev, gemm_timer=None):
         torch.cuda.reset_peak_memory_stats()
     gen = torch.Generator(device=dev).manual_seed(1 + rank)
     N = args.batch
+    last = [None]
 
     def step():
         # batch[:, 0] is the MMLU answer position, [:, 1:-1] the input, [:, 2:] the target
         batch = torch.randint(3, VOCAB, [N, S + 2], device=dev, generator=gen)
-        tuner.training_step(batch, pq_loss=(tuning == 'sparse'))
+        last[0] = tuner.training_step(batch, pq_loss=(tuning == 'sparse'))
 
     rec = {}
     if world > 1:
@@ -318,6 +343,8 @@ def model_record(tuning, args, world, rank, dev, gemm_timer=None):
             # ring / tree-independent "bus bandwidth" of an all-reduce: 2 (N - 1) / N of the bytes
             rec['allreduce_bus_gbs'] = 2.0 * (world - 1) / world * nbytes / (ms * 1e-3) / 1e9
             rec['allreduce_sampled'] = len(tuner.allreduce_events)
+    if dump is not None and rank == 0:
+        rec['dumped'] = dump_outputs(dump, tuner, last[0])
     del model, tuner
     if not CPU_REHEARSAL:
         _release()
@@ -694,7 +721,12 @@ def main():
                          'CPU form; the line says "rehearsal" and is not a measurement')
     ap.add_argument('--cpu-batch', type=int, default=2)
     ap.add_argument('--cpu-seqs', type=int, default=16)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the headline step returned in its last '
+                         'step (loss, clip norm, updated trainable parameters) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))         # before anything touches a GPU
@@ -740,7 +772,7 @@ def main():
             dist.init_process_group(args.backend)
 
     if args.rehearse_cpu:
-        rec = model_record('full', args, world, rank, dev)
+        rec = model_record('full', args, world, rank, dev, dump=args.dump_outputs)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -760,7 +792,7 @@ def main():
     ext.load_library()        # fail loudly when the HIP library is missing
 
     gemm_timer = None if args.no_gemm_events else GemmTimer()
-    sparse = model_record('sparse', args, world, rank, dev, gemm_timer)
+    sparse = model_record('sparse', args, world, rank, dev, gemm_timer, dump=args.dump_outputs)
     gemm = gemm_timer.summary() if gemm_timer is not None else None
     if gemm_timer is not None:
         gemm_timer.records.clear()
@@ -793,6 +825,8 @@ def main():
         'peak_hbm_gb': sparse['peak_hbm_gb'],
         'trainable_params': sparse['trainable_params'], 'total_params': sparse['total_params'],
     }
+    if 'dumped' in sparse:
+        result['dumped_outputs'] = sparse['dumped']
     if world > 1:
         result['ranks'] = dist.get_world_size()
         result['backend'] = dist.get_backend()

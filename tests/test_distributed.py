@@ -266,3 +266,24 @@ def test_bench_under_a_launcher_still_checks_the_world_size():
     res = _run_bench('--gpus', '2', '--rehearse-cpu', '--config', 'tiny-rehearsal',
                      env={'WORLD_SIZE': '1', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert res.returncode != 0 and 'WORLD_SIZE=1 but --gpus 2' in res.stderr
+
+
+def test_bench_dump_outputs_are_the_last_steps_and_repeat(tmp_path):
+    """`--dump-outputs DIR`: float32 / float64 arrays of the last timed step, within 64 MB; the same
+    arguments give the same arrays, and one more timed step gives different ones."""
+    import json
+    import numpy as np
+    dumps = {}
+    for tag, steps in (('a', '2'), ('b', '2'), ('c', '3')):
+        res = _run_bench('--gpus', '1', '--rehearse-cpu', '--config', 'tiny-rehearsal',
+                         '--steps', steps, '--warmup', '1', '--dump-outputs', str(tmp_path / tag))
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][0])
+        assert line['steps'] == int(steps) and line['ms_per_step'] > 0
+        names = sorted(os.listdir(str(tmp_path / tag)))
+        dumps[tag] = {n: np.load(str(tmp_path / tag / n)) for n in names}
+    assert sorted(dumps['a']) == ['grad_norm.npy', 'loss.npy', 'trainable_params.npy']
+    assert all(a.dtype in (np.float32, np.float64) for a in dumps['a'].values())
+    assert sum(a.nbytes for a in dumps['a'].values()) <= 64 << 20
+    assert all(np.array_equal(dumps['a'][n], dumps['b'][n]) for n in dumps['a'])
+    assert not np.array_equal(dumps['a']['trainable_params.npy'], dumps['c']['trainable_params.npy'])

@@ -43,7 +43,7 @@ extern "C" {
 #define SPT_EUNSUP (-3)   /* combination the kernels do not implement */
 
 /* ABI version; bump on any signature change. */
-#define SPT_ABI_VERSION 39
+#define SPT_ABI_VERSION 40
 int spt_abi_version(void);
 const char *spt_strerror(int code);
 
@@ -520,6 +520,37 @@ int spt_grouped_gemm_pdot_width(int n);
  * into its bf16 parts inside the kernel -- no image of the activation is needed at all;
  * 0 = from the fp32 operands through registers (k % 32 != 0, or no w_image). */
 int spt_grouped_gemm_image_path(const SptGroupedGemm *desc);
+
+/*
+ * The weight gradient of a grouped linear (ABI 40): a grouped product whose contraction runs over
+ * the ragged bucket rows.  For every group g, over the rows p in [offsets[g], offsets[g+1]):
+ *     out[g * group_stride + n * ldn + k] = sum_p rowscale[p] * G[srcG(p), n] * A[srcA(p), k]
+ *     dbias[g * n + n']                   = sum_p rowscale[p] * G[srcG(p), n']     (dbias != NULL)
+ *     srcG(p) = gather_g ? gather_g[p] : p,   srcA(p) = gather_a ? gather_a[p] : p
+ * i.e. dW_g = dY_g^T . A_g in the layout (n, k, group_stride, ldn, 1) of the forward's W_g view:
+ * the routed FFN's fc1 / gate / side gradients with G = dS [n_rows, block] in bucket order and
+ * A = x gathered by token, fc2 / down with G = dy gathered by token and A = h in bucket order.
+ * G [*, ldg] (ldg >= n), A [*, lda] (lda >= k); gather_g / gather_a / rowscale [n_rows] may be NULL,
+ * offsets [n_groups + 1] int32 is DEVICE memory (nondecreasing, offsets[n_groups] <= n_rows; the
+ * bucket sizes are never read on the host).  Every element of out the groups address, and every
+ * element of dbias, is written, zeros for a group without rows: no memset needed.
+ * Arithmetic as spt_grouped_gemm: split-bf16 operands, three v_mfma_f32_32x32x16_bf16 per product,
+ * fp32 accumulation, <= 2^-16 relative error per product.  The rows of every group are cut into
+ * chunks of a size that depends on n_rows alone; each chunk's product goes to `workspace`, and a
+ * second launch adds a group's chunks in chunk order: two calls give bitwise-equal results, no
+ * inter-workgroup flags or atomics, no allocation, safe under graph capture.
+ * workspace: spt_grouped_gemm_wgrad_workspace_bytes(n_rows, n_groups, n, k) bytes of device scratch
+ * (> 0, never smaller for more rows; independent of the bucket sizes).
+ * Requires n, k, ldg, lda, ldn and group_stride multiples of 4 and G, A, out, dbias and workspace
+ * 16-byte aligned (SPT_ESHAPE); SPT_EINVAL for a NULL G / A / offsets / out / workspace, n_groups < 1,
+ * n_rows < 0, n or k <= 0, ldg < n, lda < k or ldn < k -- all checked before any launch.
+ */
+long long spt_grouped_gemm_wgrad_workspace_bytes(long long n_rows, int n_groups, int n, int k);
+int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32_t *gather_g,
+                           const float *a, long long lda, const int32_t *gather_a,
+                           const float *rowscale, const int32_t *offsets, int n_groups,
+                           long long n_rows, int n, int k, float *out, long long group_stride,
+                           long long ldn, float *dbias, void *workspace, void *stream);
 
 /*
  * The pre-split image of an fp32 matrix [rows, cols] (leading dimension ld, ld % 4 == 0,

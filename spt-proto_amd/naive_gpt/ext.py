@@ -75,6 +75,10 @@ _PROTOTYPES = {
     'spt_grouped_gemm_fused': ([_c_ptr, _c_ptr], _c_int),
     'spt_grouped_gemm_pdot_width': ([_c_int], _c_int),
     'spt_grouped_gemm_image_path': ([_c_ptr], _c_int),
+    'spt_grouped_gemm_wgrad_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
+    'spt_grouped_gemm_wgrad': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, ctypes.c_longlong] + [_c_ptr] * 3
+                               + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
+                                  ctypes.c_longlong] + [_c_ptr] * 3, _c_int),
     'spt_split_bf16_bytes': ([ctypes.c_longlong, _c_int], ctypes.c_size_t),
     'spt_split_bf16': ([_c_ptr, _c_ptr, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_ptr], _c_int),
     'spt_rotary': ([_c_ptr, _c_int, _c_int, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr] + [_c_int] * 5 + [_c_ptr],
@@ -118,7 +122,7 @@ _PROTOTYPES = {
     'spt_softmax_backward_clamped': ([_c_ptr] * 5 + [_c_f32, _c_f32, _c_ptr] + [_c_int] * 3 + [_c_ptr],
                                      _c_int),
 }
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 _lib = None
 
@@ -989,6 +993,60 @@ def grouped_gemm(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Tensor,
     if rc != 0:
         _raise(lib, rc, 'grouped_gemm')
     return out
+
+
+def grouped_gemm_wgrad(grad: torch.Tensor, a: torch.Tensor, offsets: torch.Tensor, view, n_rows: int,
+                       gather_grad: torch.Tensor = None, gather_a: torch.Tensor = None,
+                       rowscale: torch.Tensor = None, out: torch.Tensor = None, want_bias: bool = False):
+    """``spt_grouped_gemm_wgrad``: the weight gradient of a grouped linear, contracted over the ragged
+    bucket rows.  For group g (rows p in offsets[g] .. offsets[g + 1] - 1, device int32)
+    ``dW_g(n, k) = sum_p rowscale[p] grad[gather_grad[p], n] a[gather_a[p], k]``, written at
+    ``out.flatten()[g * group_stride + n * ldn + k]`` with ``view = (n, k, group_stride, ldn, 1)``
+    (the forward's W_g view: the gradient lands in the parameter's own layout), and with
+    ``want_bias`` ``dbias[g, n] = sum_p rowscale[p] grad[gather_grad[p], n]``.  Every element of
+    ``out`` that a group addresses is written (zeros for an empty group).  -> (out, dbias | None);
+    ``out`` defaults to a new contiguous tensor over the view's extent (zeros where no group reaches:
+    none for the routed FFN's fc1 / fc2 views, which tile their weights exactly)."""
+    n, k, gstride, ldn, ldk = view
+    _require(ldk == 1, 'grouped_gemm_wgrad: k-contiguous views only (ldk == 1)')
+    n_groups = offsets.numel() - 1
+    for t, name in ((grad, 'grad'), (a, 'a')):
+        _check_type(t, torch.float32, name)
+        _require(t.is_cuda and t.dim() == 2 and t.stride(1) == 1, name + ': CUDA [rows, cols], unit inner stride')
+    _require(grad.size(1) == n and a.size(1) == k, 'grouped_gemm_wgrad: grad [*, n], a [*, k]')
+    _check_type(offsets, torch.int32, 'offsets')
+    _require(offsets.is_cuda and offsets.is_contiguous() and n_groups >= 1, 'offsets: [G + 1] int32 on the device')
+    for t, name in ((gather_grad, 'gather_grad'), (gather_a, 'gather_a')):
+        if t is not None:
+            _check_type(t, torch.int32, name)
+            _require(t.is_contiguous() and t.numel() == n_rows, name + ': one int32 per row')
+    if rowscale is not None:
+        _check_type(rowscale, torch.float32, 'rowscale')
+        _require(rowscale.is_contiguous() and rowscale.numel() == n_rows, 'rowscale: one float per row')
+    if gather_grad is None:
+        _require(grad.size(0) >= n_rows, 'grad: a row per row without gather_grad')
+    if gather_a is None:
+        _require(a.size(0) >= n_rows, 'a: a row per row without gather_a')
+    dev = _same_device(grad, a, offsets)
+    lib = load_library()
+    with _on(dev):
+        extent = (n_groups - 1) * gstride + (n - 1) * ldn + k
+        if out is None:
+            alloc = torch.empty if n_groups * n * k == extent else torch.zeros
+            out = alloc([extent], dtype=torch.float32, device=dev)
+        _check_type(out, torch.float32, 'out')
+        _require(out.is_contiguous() and out.device == dev, 'out: contiguous on the device of grad')
+        _require(out.numel() >= extent, 'out: too small for the view')
+        dbias = torch.empty([n_groups, n], dtype=torch.float32, device=dev) if want_bias else None
+        work = torch.empty([lib.spt_grouped_gemm_wgrad_workspace_bytes(n_rows, n_groups, n, k)],
+                           dtype=torch.uint8, device=dev)
+        rc = lib.spt_grouped_gemm_wgrad(grad.data_ptr(), grad.stride(0), _ptr(gather_grad),
+                                        a.data_ptr(), a.stride(0), _ptr(gather_a), _ptr(rowscale),
+                                        offsets.data_ptr(), n_groups, n_rows, n, k, out.data_ptr(),
+                                        gstride, ldn, _ptr(dbias), work.data_ptr(), _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'grouped_gemm_wgrad')
+    return out, dbias
 
 
 class _GroupedDesc(ctypes.Structure):

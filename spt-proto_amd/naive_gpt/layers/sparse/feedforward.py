@@ -59,8 +59,8 @@ class RoutedFFN(layers.Feedforward):
         """Frozen base weights on the GPU (a stage-'ffn'-only model, inference): the same device-side
         bucketing and grouped matrix-core GEMMs as the LoRA variant (layers/sparse/grouped.py), no
         host synchronisation -- the reference's loop reads every block's row count on the host
-        (feedforward.py:66-85).  Trainable weights keep the loop (their gradients are per-bucket
-        products this library does not form)."""
+        (feedforward.py:66-85).  Trainable weights take _forward_trainable when
+        grouped.TRAINABLE_WEIGHTS is on, the loop otherwise."""
         from . import grouped
         nb, bs, d = self.n_blocks, self.block_size, self.d_model
         prob = self.router(x)
@@ -72,6 +72,26 @@ class RoutedFFN(layers.Feedforward):
                                     (d, bs, bs, self.d_feedforward, 1))
         return _combine(ys, bk, x) + self.fc2.bias.view([1, -1])
 
+    def _forward_trainable(self, x: torch.Tensor):
+        """Trainable base weights on the grouped path (grouped.TRAINABLE_WEIGHTS): the same
+        bucketing and block GEMMs, the weight gradients as grouped products over the bucket rows
+        (grouped.RoutedFFNTrain).  The router only picks the blocks: no gradient reaches it."""
+        from . import grouped
+        prob = self.router(x)
+        bk = grouped.make_buckets(prob.detach(), k=self.n_blocks // 2)
+        return grouped.RoutedFFNTrain.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight,
+                                            self.fc2.bias, bk.token, bk.offsets, bk.pos, self.n_blocks,
+                                            grouped.activation_code(self.activation))
+
+    def _trainable_unusable(self, x: torch.Tensor):
+        from . import grouped
+        if not grouped.TRAINABLE_WEIGHTS:
+            return None, False
+        if self.d_model % 4 != 0 or self.block_size % 4 != 0:
+            return 'd_model {} / block {}: multiples of 4 only'.format(self.d_model, self.block_size), True
+        return grouped.trainable_unusable(x, grouped.activation_code(self.activation), self.fc1.weight,
+                                          self.fc1.bias, self.fc2.weight, self.fc2.bias), True
+
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         x = x.view([-1, self.d_model])
@@ -79,9 +99,16 @@ class RoutedFFN(layers.Feedforward):
                 and self.d_model % 4 == 0 and self.block_size % 4 == 0:
             ext.note_path('routed_ffn_plain', 'grouped')
             return self._forward_grouped(x.contiguous()).view(x_size)
-        ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
-                      why=lambda: 'x {} {}, trainable weights: {}'.format(
-                          tuple(x.shape), x.dtype, self.fc1.weight.requires_grad))
+        why, on = self._trainable_unusable(x)
+        if on and why is None:
+            ext.note_path('routed_ffn_plain', 'grouped_trainable')
+            return self._forward_trainable(x.contiguous()).view(x_size)
+        if on:
+            ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda, why=lambda: why)
+        else:
+            ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
+                          why=lambda: 'x {} {}, trainable weights: {}'.format(
+                              tuple(x.shape), x.dtype, self.fc1.weight.requires_grad))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 2)
         w1 = self.fc1.weight.view([self.n_blocks, self.block_size, -1])
@@ -132,6 +159,24 @@ class RoutedLLaMaFFN(layers.LLaMaFeedforward):
         ys = grouped.grouped_linear(h, self.down.weight, bk.offsets, (d, bs, bs, self.d_feedforward, 1))
         return _combine(ys, bk, x)
 
+    def _forward_trainable(self, x: torch.Tensor):
+        """see RoutedFFN._forward_trainable (grouped.RoutedLLaMAFFNTrain)"""
+        from . import grouped
+        prob = self.router(x)
+        bk = grouped.make_buckets(prob.detach(), k=self.n_blocks // 4)
+        return grouped.RoutedLLaMAFFNTrain.apply(x, self.gate.weight, self.side.weight, self.down.weight,
+                                                 bk.token, bk.offsets, bk.pos, self.n_blocks, self.activation)
+
+    def _trainable_unusable(self, x: torch.Tensor):
+        from . import grouped
+        if not grouped.TRAINABLE_WEIGHTS:
+            return None, False
+        if self.n_blocks < 4 or self.d_model % 4 != 0 or self.block_size % 4 != 0:
+            return 'n_blocks {}, d_model {} / block {}: >= 4 blocks, multiples of 4 only'.format(
+                self.n_blocks, self.d_model, self.block_size), True
+        # (any activation: the gating product and its derivative are elementwise)
+        return grouped.trainable_unusable(x, 0, self.gate.weight, self.side.weight, self.down.weight), True
+
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         x = x.view([-1, self.d_model])
@@ -139,9 +184,16 @@ class RoutedLLaMaFFN(layers.LLaMaFeedforward):
                 and self.d_model % 4 == 0 and self.block_size % 4 == 0:
             ext.note_path('routed_ffn_plain', 'grouped')
             return self._forward_grouped(x.contiguous()).view(x_size)
-        ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
-                      why=lambda: 'x {} {}, trainable weights: {}'.format(
-                          tuple(x.shape), x.dtype, self.gate.weight.requires_grad))
+        why, on = self._trainable_unusable(x)
+        if on and why is None:
+            ext.note_path('routed_ffn_plain', 'grouped_trainable')
+            return self._forward_trainable(x.contiguous()).view(x_size)
+        if on:
+            ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda, why=lambda: why)
+        else:
+            ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
+                          why=lambda: 'x {} {}, trainable weights: {}'.format(
+                              tuple(x.shape), x.dtype, self.gate.weight.requires_grad))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 4)
         gate = self.gate.weight.view([self.n_blocks, self.block_size, -1])

@@ -10,6 +10,10 @@ gathers and per-block cuBLAS calls (``layers/tuning/lora_ffn.py:87-111``).
 
 Row space: P = T * k rows, row p = the p-th (token, block) pair in block-major order
 (stable in the token id, i.e. the reference's ``x[mask]`` order inside each block).
+
+Trainable base weights (the plain RoutedFFN / RoutedLLaMaFFN in training) take the grouped path
+too when ``TRAINABLE_WEIGHTS`` is on: their gradients are grouped products contracted over the
+bucket rows (``spt_grouped_gemm_wgrad``), written straight into the parameters' layouts.
 """
 import os
 from typing import NamedTuple
@@ -89,6 +93,11 @@ def make_buckets(prob: torch.Tensor, k: int, scale: float = 1.0) -> Buckets:
                    pos=pos.view(n_tokens, k).int())
 
 
+# Trainable base weights of the plain routed FFNs on the grouped path (RoutedFFNTrain /
+# RoutedLLaMAFFNTrain below) instead of the per-block loop.  Opt-in until it is measured as the
+# default; read at call time (tests flip it).
+TRAINABLE_WEIGHTS = os.environ.get('SPT_ROUTED_TRAINABLE', '0') != '0'
+
 COEFF_FLOOR = 1e-12
 # h (one reader) goes to its GEMM as fp32 rows, no image: -0.36 ms per configs[2] step, A/B on one
 # box (the same for x: +0.26 ms, for dy: +-0: both keep their images)
@@ -122,12 +131,15 @@ class GroupedLinear(torch.autograd.Function):
                                gather=gather, bias=bias, rowscale=rowscale)
         ctx.view = view
         ctx.a_rows = a.size(0)
-        ctx.save_for_backward(weight, offsets, gather_long, rowscale, out)
+        # (a and gather only when the weight wants a gradient: the frozen path keeps no activation)
+        wants_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[6]
+        ctx.save_for_backward(weight, offsets, gather_long, rowscale, out,
+                              a if wants_w else None, gather if wants_w else None)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        weight, offsets, gather_long, rowscale, out = ctx.saved_tensors
+        weight, offsets, gather_long, rowscale, out, a, gather = ctx.saved_tensors
         n, k, gstride, ldn, ldk = ctx.view
         n_groups = offsets.numel() - 1
         grad_out = grad_out.contiguous()
@@ -144,14 +156,181 @@ class GroupedLinear(torch.autograd.Function):
             else:
                 grad_a = torch.zeros([ctx.a_rows, k], dtype=rows.dtype, device=rows.device)
                 grad_a.index_add_(0, gather_long, rows)
-        if ctx.needs_input_grad[1]:
-            raise NotImplementedError('GroupedLinear: weight gradients (frozen base only)')
-        return grad_a, None, None, None, None, None, None, grad_scale
+        grad_w = grad_bias = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[6]:
+            # dW_g(n, kk) = sum over the rows p of g of s[p] dout[p, n] a[src(p), kk]; d bias[g, n] =
+            # sum_p s[p] dout[p, n]: one grouped product over the bucket rows, into W's own layout
+            if ldk != 1:
+                raise NotImplementedError('GroupedLinear: weight gradients of k-contiguous views only')
+            covered = n_groups * n * k == weight.numel()
+            grad_w = torch.empty_like(weight) if covered else torch.zeros_like(weight)
+            _, grad_bias = ext.grouped_gemm_wgrad(grad_out, a, offsets, ctx.view, grad_out.size(0),
+                                                  gather_a=gather, rowscale=rowscale, out=grad_w.view(-1),
+                                                  want_bias=ctx.needs_input_grad[6])
+            if not ctx.needs_input_grad[1]:
+                grad_w = None
+        return grad_a, grad_w, None, None, None, None, grad_bias, grad_scale
 
 
 def grouped_linear(a, weight, offsets, view, gather=None, gather_long=None, bias=None,
                    rowscale=None):
     return GroupedLinear.apply(a, weight, offsets, view, gather, gather_long, bias, rowscale)
+
+
+def trainable_unusable(x: torch.Tensor, act, *weights):
+    """None when the trainable grouped path takes these operands, else the reason it does not."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        return 'x {} {} (fp32 CUDA activations only)'.format(tuple(x.shape), x.dtype)
+    if act is None:
+        return 'activation without a fused epilogue (ReLU, exact GELU, SiLU)'
+    for w in weights:
+        if not w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
+            return 'weight {} {}: fp32 contiguous CUDA weights only'.format(tuple(w.shape), w.dtype)
+    return None
+
+
+def _fresh_image(w: torch.Tensor):
+    """The split image of a TRAINABLE weight: made from its current values every call (a cache
+    keyed on `_version` misses writes through `.data`, which optimizers and loaders use)."""
+    return ext.split_bf16(w.detach())
+
+
+class RoutedFFNTrain(torch.autograd.Function):
+    """y = RoutedFFN(x) with trainable base weights (reference: layers/sparse/feedforward.py:66-85;
+    the blocks are not weighted by the router, which therefore gets no gradient):
+
+        h  = act(x[token] W1_g^T + b1_g)      spt_grouped_gemm_fused, EPI_ACT
+        ys = h W2_g^T;  y = b2 + sum over the token's rows of ys     fused GEMM + spt_rows_combine
+      backward
+        ds  = (dy[token] W2_g) * act'(s)      EPI_DACT
+        dW2 = dy[token]^T h per block,  dW1 = ds^T x[token] per block (+ db1)   spt_grouped_gemm_wgrad
+        dx  = sum over the token's rows of ds W1_g
+
+    For ReLU the derivative must be that of the EXACT fp32 pre-activation (a split-sign mask is an
+    O(1) error in a row of dW1): the forward is the fused EPI_ACT with the row norms of x and of the
+    current W1, which recomputes the elements within the split's error of zero in fp32, and the
+    backward's mask is h > 0.  Norms and images are formed from the weights' values at the call."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, token, offsets, pos, nb: int, act: int):
+        d_ff, d = w1.shape
+        bs, rows = d_ff // nb, token.numel()
+        relu = act == ext.ACT_RELU
+        imgs = _images_usable(x, w1, w2, d, bs)
+        w1_img, w2_img = (_fresh_image(w1), _fresh_image(w2)) if imgs else (None, None)
+        h, s = ext.grouped_gemm_fused(
+            x, w1, offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1, n_rows=rows,
+            gather=token, bias=b1.detach().contiguous(), epilogue=ext.EPI_ACT, activation=act,
+            keep_preact=not relu, w_image=w1_img,
+            a_norm=ext.row_norms(x) if relu else None, w_norm=ext.row_norms(w1) if relu else None)
+        ys = ext.grouped_gemm_fused(h, w2, offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff,
+                                    w_ldk=1, n_rows=rows, w_image=w2_img)
+        y = ext.rows_combine(ys, pos, bias=b2.detach().contiguous())
+        ctx.nb, ctx.act, ctx.imgs = nb, act, (w1_img, w2_img)
+        ctx.save_for_backward(x, h, s, w1, w2, token, offsets, pos)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, h, s, w1, w2, token, offsets, pos = ctx.saved_tensors
+        w1_img, w2_img = ctx.imgs
+        nb, act = ctx.nb, ctx.act
+        d_ff, d = w1.shape
+        bs, rows = d_ff // nb, token.numel()
+        dy = dy.contiguous()
+        ds, _, _ = ext.grouped_gemm_fused(
+            dy, w2, offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff, n_rows=rows,
+            gather=token, epilogue=ext.EPI_DACT, activation=act, h_in=h, s_in=s, w_image=w2_img,
+            raw_dots=True)
+        grad_w2 = grad_b2 = grad_w1 = grad_b1 = grad_x = None
+        if ctx.needs_input_grad[3]:
+            grad_w2, _ = ext.grouped_gemm_wgrad(dy, h, offsets, (d, bs, bs, d_ff, 1), rows, gather_grad=token)
+            grad_w2 = grad_w2.view(d, d_ff)
+        if ctx.needs_input_grad[4]:
+            grad_b2 = dy.sum(dim=0)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grad_w1, grad_b1 = ext.grouped_gemm_wgrad(ds, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                                      gather_a=token, want_bias=ctx.needs_input_grad[2])
+            grad_w1 = grad_w1.view(d_ff, d) if ctx.needs_input_grad[1] else None
+            grad_b1 = grad_b1.view(d_ff) if grad_b1 is not None else None
+        if ctx.needs_input_grad[0]:
+            dxs = ext.grouped_gemm_fused(ds, w1, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1,
+                                         w_ldk=d, n_rows=rows, w_image=w1_img)
+            grad_x = ext.rows_combine(dxs, pos)
+        return grad_x, grad_w1, grad_b1, grad_w2, grad_b2, None, None, None, None, None
+
+
+class RoutedLLaMAFFNTrain(torch.autograd.Function):
+    """y = RoutedLLaMaFFN(x) with trainable base weights (reference: feedforward.py:133-187):
+
+        g = x[token] G_g^T,  sd = x[token] S_g^T      two grouped GEMMs
+        h = act(g) * sd                               spt_swiglu_forward (SiLU), else torch
+        y = sum over the token's rows of h D_g^T      fused GEMM + spt_rows_combine
+      backward
+        dh = dy[token] D_g;  dg, dsd through h = act(g) * sd     spt_swiglu_backward (SiLU)
+        dD = dy[token]^T h,  dG = dg^T x[token],  dS = dsd^T x[token] per block   spt_grouped_gemm_wgrad
+        dx = sum over the token's rows of dg G_g + dsd S_g      (the second GEMM accumulates)"""
+
+    @staticmethod
+    def forward(ctx, x, wg, ws, wd, token, offsets, pos, nb: int, activation):
+        d_ff, d = wg.shape
+        bs, rows = d_ff // nb, token.numel()
+        imgs = _images_usable(x, wg, wd, d, bs)
+        wg_img, ws_img, wd_img = (_fresh_image(wg), _fresh_image(ws), _fresh_image(wd)) if imgs \
+            else (None, None, None)
+
+        def up(w, img):
+            return ext.grouped_gemm_fused(x, w, offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d,
+                                          w_ldk=1, n_rows=rows, gather=token, w_image=img)
+
+        g, sd = up(wg, wg_img), up(ws, ws_img)
+        silu = isinstance(activation, torch.nn.SiLU) and ext.swiglu_supported(g, sd)
+        ext.note_path('swiglu', 'kernel' if silu else 'torch', fallback=not silu,
+                      why=lambda: 'activation {} on {}'.format(type(activation).__name__, tuple(g.shape)))
+        h = ext.swiglu_forward(g, sd) if silu else activation(g) * sd
+        ys = ext.grouped_gemm_fused(h, wd, offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff,
+                                    w_ldk=1, n_rows=rows, w_image=wd_img)
+        y = ext.rows_combine(ys, pos)
+        ctx.nb, ctx.activation, ctx.silu, ctx.imgs = nb, activation, silu, (wg_img, ws_img, wd_img)
+        ctx.save_for_backward(x, g, sd, h, wg, ws, wd, token, offsets, pos)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, sd, h, wg, ws, wd, token, offsets, pos = ctx.saved_tensors
+        wg_img, ws_img, wd_img = ctx.imgs
+        nb = ctx.nb
+        d_ff, d = wg.shape
+        bs, rows = d_ff // nb, token.numel()
+        dy = dy.contiguous()
+        dh = ext.grouped_gemm_fused(dy, wd, offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1,
+                                    w_ldk=d_ff, n_rows=rows, gather=token, w_image=wd_img)
+        grad_wg = grad_ws = grad_wd = grad_x = None
+        if ctx.needs_input_grad[3]:
+            grad_wd, _ = ext.grouped_gemm_wgrad(dy, h, offsets, (d, bs, bs, d_ff, 1), rows, gather_grad=token)
+            grad_wd = grad_wd.view(d, d_ff)
+        if ctx.silu:
+            dg, dsd, _, _, _ = ext.swiglu_backward(dh, g, sd)
+        else:
+            with torch.enable_grad():
+                g_ = g.detach().requires_grad_(True)
+                ag = ctx.activation(g_)
+                dg, = torch.autograd.grad(ag, g_, dh * sd)
+            dsd = dh * ag.detach()
+        del dh
+        if ctx.needs_input_grad[1]:
+            grad_wg = ext.grouped_gemm_wgrad(dg, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                             gather_a=token)[0].view(d_ff, d)
+        if ctx.needs_input_grad[2]:
+            grad_ws = ext.grouped_gemm_wgrad(dsd, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                             gather_a=token)[0].view(d_ff, d)
+        if ctx.needs_input_grad[0]:
+            dxs = ext.grouped_gemm_fused(dg, wg, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1,
+                                         w_ldk=d, n_rows=rows, w_image=wg_img)
+            ext.grouped_gemm_fused(dsd, ws, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1,
+                                   w_ldk=d, n_rows=rows, w_image=ws_img, out=dxs, accumulate=True)
+            grad_x = ext.rows_combine(dxs, pos)
+        return grad_x, grad_wg, grad_ws, grad_wd, None, None, None, None, None
 
 
 def usable(x: torch.Tensor, *frozen_weights) -> bool:

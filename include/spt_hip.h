@@ -553,6 +553,57 @@ int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32_t *gather_
                            long long ldn, float *dbias, void *workspace, void *stream);
 
 /*
+ * bf16 storage for the grouped GEMM and its weight gradient (additive under ABI 40).
+ *
+ * Arithmetic contract: fp32 accumulation of the EXACT products of the stored bf16 values (one
+ * v_mfma_f32_32x32x16_bf16 per product, no split), every result rounded once to bf16 (round to
+ * nearest even) when it is stored.  Epilogue arithmetic (rowscale, bias, activation, derivative) is
+ * fp32 on the accumulator, as in spt_grouped_gemm_fused.
+ *
+ * spt_grouped_gemm_bf16: the product of spt_grouped_gemm_fused without the K extension, the images,
+ * the ReLU norms / queue, a_seg_k and b2_seg_stride:
+ *     out[p, n] = act( rowscale[p] * (sum_k A[src(p), k] W_g(n, k) + bias[g, n]) )     (SPT_EPI_ACT)
+ * a, w, bias, out, out2, h_in, s_in: bf16 (raw 16-bit storage); rowscale [n_rows] fp32, pdot_* fp32.
+ * SPT_EPI_DACT: out = v * act'(s) with s_in (or h_in for ReLU) bf16; pdot_main / pdot_act optional
+ * (both or neither).  Both operands go global -> LDS by LDS-DMA straight from the tensors.
+ * Requires (SPT_ESHAPE): k % 64 == 0, lda % 8 == 0, w_group_stride % 8 == 0, a and w 16-byte aligned;
+ * w_ldk == 1: w_ldn % 8 == 0, w_ldn >= k; w_ldn == 1: w_ldk % 8 == 0, w_ldk >= n, n % 32 == 0;
+ * out, out2, bias, h_in, s_in 8-byte aligned.  ldo: row stride (elements) of out / out2 / h_in / s_in.
+ */
+typedef struct SptGroupedGemmBf16 {
+    const void *a;             /* bf16 [*, lda] */
+    const int32_t *gather;
+    const void *w;             /* bf16, W_g(n, k) = w[g * w_group_stride + n * w_ldn + k * w_ldk] */
+    const void *bias;          /* bf16 [n_groups, n] or NULL */
+    const float *rowscale;     /* fp32 [n_rows] or NULL */
+    const int32_t *offsets;
+    void *out;                 /* bf16 [n_rows, ldo] */
+    int32_t n_rows, k, n, n_groups, lda;
+    int64_t w_group_stride;
+    int32_t w_ldn, w_ldk;
+    int64_t ldo;
+    int32_t epilogue, activation;
+    int32_t accumulate;        /* SPT_EPI_PLAIN: out = bf16(out + product) */
+    void *out2;                /* SPT_EPI_ACT: pre-activation (bf16) or NULL */
+    const void *h_in;          /* SPT_EPI_DACT */
+    const void *s_in;
+    float *pdot_main;
+    float *pdot_act;
+    int32_t pdot_ld;
+} SptGroupedGemmBf16;
+int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *desc, void *stream);
+/* spt_grouped_gemm_wgrad on bf16 G, A, out and dbias: same arguments, rules, chunking and in-order
+ * reduction (fp32 chunk partials; bitwise reproducible, no atomics, capturable); out and dbias rounded
+ * once.  Alignment: G, A, out and dbias 8-byte aligned (four bf16 per access), workspace 16-byte.  Products are exact without a rowscale; with one, rowscale * G is formed in fp32 and split
+ * (<= 2^-16 relative per product).  The workspace is spt_grouped_gemm_wgrad_bf16_workspace_bytes. */
+long long spt_grouped_gemm_wgrad_bf16_workspace_bytes(long long n_rows, int n_groups, int n, int k);
+int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const int32_t *gather_g,
+                                const void *a, long long lda, const int32_t *gather_a,
+                                const float *rowscale, const int32_t *offsets, int n_groups,
+                                long long n_rows, int n, int k, void *out, long long group_stride,
+                                long long ldn, void *dbias, void *workspace, void *stream);
+
+/*
  * The pre-split image of an fp32 matrix [rows, cols] (leading dimension ld, ld % 4 == 0,
  * 16-byte aligned): every element x as hi = bf16(x) (round to nearest even) and
  * lo = bf16(x - hi), laid out [row][ceil(cols / 32)][hi: 32 x bf16 | lo: 32 x bf16], i.e. one
@@ -756,6 +807,11 @@ int spt_rotary(const float *const *x, int n_parts, int n_rot, float *out, long l
 int spt_swiglu_forward(const float *gate, const float *side, float *h, long long n_elements, void *stream);
 int spt_swiglu_backward(const float *grad_h, const float *gate, const float *side, float *grad_gate,
                         float *grad_side, float *dots, long long rows, int n, void *stream);
+/* The same on bf16 tensors (8-byte aligned, n_elements % 4 == 0), fp32 inside, one rounding per output;
+ * the backward forms grad_gate and grad_side only (no row dots). */
+int spt_swiglu_forward_bf16(const void *gate, const void *side, void *h, long long n_elements, void *stream);
+int spt_swiglu_backward_bf16(const void *grad_h, const void *gate, const void *side, void *grad_gate,
+                             void *grad_side, long long n_elements, void *stream);
 
 /*
  * Gradient of table[ids] (the `left` table of a LoRA embedding, lora.py:118-126; autograd of
@@ -785,6 +841,10 @@ int spt_rows_combine(const float *rows, const int32_t *pos, const float *bias, f
 int spt_rows_combine_side(const float *rows, const int32_t *pos, const float *bias, const float *side,
                           const float *side_w, int n_side, float *out, int n_tokens, int k, int d,
                           void *stream);
+/* spt_rows_combine on bf16 rows / bias / out (8-byte aligned): summed in fp32 in the same order,
+ * rounded once. */
+int spt_rows_combine_bf16(const void *rows, const int32_t *pos, const void *bias, void *out,
+                          int n_tokens, int k, int d, void *stream);
 
 #ifdef __cplusplus
 }

@@ -244,6 +244,20 @@ __device__ __forceinline__ void gg_scale_rows(const GroupedArgs &g, f32x16 (&acc
         }
 }
 
+// bf16 storage (spt_grouped_gemm_bf16 / _wgrad_bf16 / spt_rows_combine_bf16): widening is exact,
+// narrowing is v_cvt_pk_bf16_f32 (round to nearest even), once per stored value
+__device__ __forceinline__ float gg_bf(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
+__device__ __forceinline__ float4 gg_bf4(const unsigned short *p) {         // 8-byte aligned
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xffff0000u),
+                       __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xffff0000u));
+}
+__device__ __forceinline__ unsigned gg_bf2_pack(float a, float b) {
+    const gg_f32x2 x = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(x, gg_bf16x2));
+}
+__device__ __forceinline__ unsigned short gg_bf_round(float a) { return (unsigned short)gg_bf2_pack(a, 0.0f); }
+
 // Epilogue of a (32 NI x 2) x 128 tile.  MFMA C layout: acc[i][j][r] =
 // C[32 i + (r & 3) + 8 (r >> 2) + 4 (l >> 5)][32 j + (l & 31)] of the wave's (32 NI) x 64
 // part.  Each wave transposes it through LDS, 32 rows at a time, into a row layout -- 16
@@ -251,7 +265,8 @@ __device__ __forceinline__ void gg_scale_rows(const GroupedArgs &g, f32x16 (&acc
 // h / s tiles of EPI_DACT, the bias) is 16 bytes per lane and 256 contiguous bytes per row,
 // and a row dot is a 16-lane DPP reduction.  The caller has synchronised the workgroup: the
 // operand tiles in `smem` are dead.
-template <int NI, int EPI>
+// (BF16: bias, out, out2, h_in and s_in hold bf16; the pdot rows are fp32 and optional)
+template <int NI, int EPI, bool BF16 = false>
 __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
                                             f32x16 (&acc)[NI][2], int bucket, int row_lo,
                                             int row_hi, int col_tile, int wm, int wn,
@@ -268,7 +283,15 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
     const bool vec = (g.N & 3) == 0;
     const bool vec_row = (g.ldo & 3) == 0;        // 16-byte aligned pieces of the N-wide rows
     float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (g.bias) {
+    if (BF16 && g.bias) {
+        const unsigned short *bp = reinterpret_cast<const unsigned short *>(g.bias) + (size_t)bucket * g.N + n;
+        if (vec) {
+            if (n < g.N) bias4 = gg_bf4(bp);
+        } else {
+            bias4.x = n + 0 < g.N ? gg_bf(bp[0]) : 0.f; bias4.y = n + 1 < g.N ? gg_bf(bp[1]) : 0.f;
+            bias4.z = n + 2 < g.N ? gg_bf(bp[2]) : 0.f; bias4.w = n + 3 < g.N ? gg_bf(bp[3]) : 0.f;
+        }
+    } else if (g.bias) {
         const float *bp = g.bias + (size_t)bucket * g.N + n;
         if (vec) {
             if (n < g.N) bias4 = *reinterpret_cast<const float4 *>(bp);
@@ -304,7 +327,17 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
         // (rows past the bucket end: clamped, never used)
         auto load_saved = [&](int t) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (EPI == EPI_DACT) {
+            if (EPI == EPI_DACT && BF16) {
+                const int p = min(row_lo + wm + 32 * i + rrow + 4 * t, row_hi - 1);
+                const size_t at = (size_t)p * g.ldo + n;
+                const unsigned short *sb = reinterpret_cast<const unsigned short *>(sh);
+                if (vec_row && n + 3 < g.N) {
+                    v = gg_bf4(sb + at);
+                } else {
+                    v.x = n + 0 < g.N ? gg_bf(sb[at + 0]) : 0.f; v.y = n + 1 < g.N ? gg_bf(sb[at + 1]) : 0.f;
+                    v.z = n + 2 < g.N ? gg_bf(sb[at + 2]) : 0.f; v.w = n + 3 < g.N ? gg_bf(sb[at + 3]) : 0.f;
+                }
+            } else if (EPI == EPI_DACT) {
                 const int p = min(row_lo + wm + 32 * i + rrow + 4 * t, row_hi - 1);
                 const size_t at = (size_t)p * g.ldo + n;
                 if (vec_row && n + 3 < g.N) {
@@ -396,7 +429,17 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
                     todo = __ballot(cand != 0);
                 }
             }
-            if (EPI == EPI_PLAIN && g.accumulate && live) {
+            if (BF16 && EPI == EPI_PLAIN && g.accumulate && live) {
+                const unsigned short *ob = reinterpret_cast<const unsigned short *>(g.out);
+                if (vec_row && n + 3 < g.N) {
+                    const float4 o4 = gg_bf4(ob + at);
+                    c[0] += o4.x; c[1] += o4.y; c[2] += o4.z; c[3] += o4.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (n + e < g.N) c[e] += gg_bf(ob[at + e]);
+                }
+            } else if (EPI == EPI_PLAIN && g.accumulate && live) {
                 if (vec_row && n + 3 < g.N) {
                     const float4 o4 = *reinterpret_cast<const float4 *>(g.out + at);
                     c[0] += o4.x; c[1] += o4.y; c[2] += o4.z; c[3] += o4.w;
@@ -406,7 +449,23 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
                         if (n + e < g.N) c[e] += g.out[at + e];
                 }
             }
-            if (live) {
+            if (BF16 && live) {
+                unsigned short *ob = reinterpret_cast<unsigned short *>(g.out);
+                unsigned short *pb = reinterpret_cast<unsigned short *>(g.out2);
+                if (vec_row && n + 3 < g.N) {
+                    *reinterpret_cast<uint2 *>(ob + at) = make_uint2(gg_bf2_pack(c[0], c[1]), gg_bf2_pack(c[2], c[3]));
+                    if (EPI == EPI_ACT && pb)
+                        *reinterpret_cast<uint2 *>(pb + at) =
+                            make_uint2(gg_bf2_pack(pre[0], pre[1]), gg_bf2_pack(pre[2], pre[3]));
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (n + e < g.N) {
+                            ob[at + e] = gg_bf_round(c[e]);
+                            if (EPI == EPI_ACT && pb) pb[at + e] = gg_bf_round(pre[e]);
+                        }
+                }
+            } else if (live) {
                 if (vec_row && n + 3 < g.N) {
                     {
                         *reinterpret_cast<float4 *>(g.out + at) = make_float4(c[0], c[1], c[2], c[3]);
@@ -426,7 +485,7 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
             if (EPI == EPI_DACT) {
                 dot_h = group_sum<16>(dot_h);
                 dot_s = group_sum<16>(dot_s);
-                if (live && (lane & 15) == 0) {
+                if (live && (lane & 15) == 0 && (!BF16 || g.pdot_main)) {
                     g.pdot_main[(size_t)p * g.pdot_ld + pslot] = dot_h;
                     g.pdot_act[(size_t)p * g.pdot_ld + pslot] = dot_s;
                 }
@@ -530,12 +589,22 @@ __device__ __forceinline__ void gi_read(const GiLane<NI, NA> &c, const char *As,
         }
     }
 }
-template <int NI>
+// BF16 (spt_grouped_gemm_bf16): the operands ARE bf16 and a stage holds 64 k -- the "hi" fragment
+// is k 0 .. 31 of the step, the "lo" fragment k 32 .. 63 -- so a fragment pair is two plain products
+template <int NI, bool BF16 = false>
 __device__ __forceinline__ void gi_mma(const GiFrags<NI> &f, f32x16 (&acc)[NI][2]) {
 #pragma unroll
     for (int i = 0; i < NI; i++) {
-        acc[i][0] = gg_mma3(f.a[i], f.b[0], acc[i][0]);
-        acc[i][1] = gg_mma3(f.a[i], f.b[1], acc[i][1]);
+        if constexpr (BF16) {
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                acc[i][j] = gg_mma(f.a[i].hi, f.b[j].hi, acc[i][j]);
+                acc[i][j] = gg_mma(f.a[i].lo, f.b[j].lo, acc[i][j]);
+            }
+        } else {
+            acc[i][0] = gg_mma3(f.a[i], f.b[0], acc[i][0]);
+            acc[i][1] = gg_mma3(f.a[i], f.b[1], acc[i][1]);
+        }
     }
 }
 template <int NI, int NA, bool KC_B>
@@ -546,9 +615,10 @@ __device__ __forceinline__ void gi_contract(const GiLane<NI, NA> &c, const char 
     gi_mma<NI>(f, acc);
 }
 // k-step k0 .. k0 + 31 into the LDS stage at `dma` (instruction t = wave + 4 j: 1 KiB each)
-template <int NI, int NA, bool BN_LAYOUT>
+// (BF16: k-steps of 64 bf16 -- the same 128 bytes per row of a KC tile, k0 * 2 bytes into the row)
+template <int NI, int NA, bool BN_LAYOUT, bool BF16 = false>
 __device__ __forceinline__ void gi_stage(const GiLane<NI, NA> &c, char *dma, int k0) {
-    const size_t ka = (size_t)(k0 >> 5) * 128;
+    const size_t ka = BF16 ? (size_t)k0 * 2 : (size_t)(k0 >> 5) * 128;
     // (ablation builds, tools/variant.sh: wrong results, for timing -- which operand's stream
     // the k-loop waits for)
 #ifdef GG_ABL_NO_A
@@ -572,7 +642,7 @@ __device__ __forceinline__ void gi_stage(const GiLane<NI, NA> &c, char *dma, int
 // ds_reads alias scopes, and only with those does hipcc (ROCm 7.2) leave out the
 // `s_waitcnt vmcnt(0)` it otherwise puts in front of the first ds_read behind an LDS-DMA in
 // flight -- which would wait for the next tile before the current one is contracted.
-template <int NI, int NA, bool BN_LAYOUT, bool A32>
+template <int NI, int NA, bool BN_LAYOUT, bool A32, bool BF16 = false>
 __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restrict__ dma,
                                         const char *__restrict__ cur, bool prefetch, int k_next,
                                         f32x16 (&acc)[NI][2]
@@ -592,7 +662,7 @@ __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restric
 #ifdef GG_STAMP_DMA
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
 #endif
-    if (prefetch) gi_stage<NI, NA, BN_LAYOUT>(c, dma, k_next);
+    if (prefetch) gi_stage<NI, NA, BN_LAYOUT, BF16>(c, dma, k_next);
 #ifdef GG_STAMP_DMA
     __builtin_amdgcn_sched_barrier(0);
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -605,9 +675,9 @@ __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restric
 #ifdef GG_STAMP_DMA
     const unsigned long long t2 = __builtin_amdgcn_s_memtime();
 #endif
-    gi_mma<NI>(f0, acc);
+    gi_mma<NI, BF16>(f0, acc);
     __builtin_amdgcn_sched_barrier(0);
-    gi_mma<NI>(f1, acc);
+    gi_mma<NI, BF16>(f1, acc);
     __builtin_amdgcn_sched_barrier(0);
 #ifdef GG_STAMP_DMA
     const unsigned long long t3 = __builtin_amdgcn_s_memtime();
@@ -615,11 +685,17 @@ __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restric
 #endif
 }
 
-template <int BM, bool BN_LAYOUT, int EPI, bool EXT, bool A32>
+// BF16 (spt_grouped_gemm_bf16): a, w, bias and out hold bf16 (their float pointers of GroupedArgs
+// carry bf16 tensors); both operands go global -> LDS by LDS-DMA straight from the tensors, 64 k per
+// stage in the tiles' 128-byte rows (KC: chunk c = k 8 c .. 8 c + 7; NC: "part" 0 / 1 = k-rows
+// kr / 32 + kr of the step), two plain MFMAs per fragment pair; no K extension
+template <int BM, bool BN_LAYOUT, int EPI, bool EXT, bool A32, bool BF16 = false>
 __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem, int bucket,
                                               int row_lo, int row_hi, int col_tile) {
+    static_assert(!(BF16 && (EXT || A32)), "bf16: no K extension, no fp32 rows");
     constexpr int NI = BM / 64;                 // 32-row sub-blocks per wave
     constexpr int NA = BM / 32;                 // LDS-DMA instructions per wave: A tile
+    constexpr int KS = BF16 ? 2 * GG_BK : GG_BK;    // k per stage
 #ifdef GG_STAMP_DMA
     const unsigned long long t_enter = __builtin_amdgcn_s_memtime();
 #endif
@@ -654,12 +730,13 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
         const int p = min(row_lo + r, row_hi - 1);
         const long long src = g.gather ? g.gather[p] : p;
         // (A32: the fp32 rows themselves, a_rowb = 4 lda; 32 k = 128 bytes per k-step either way)
-        c.a_src[j] = (A32 ? reinterpret_cast<const char *>(g.a) : g.a_img) + src * g.a_rowb +
+        c.a_src[j] = (A32 || BF16 ? reinterpret_cast<const char *>(g.a) : g.a_img) + src * g.a_rowb +
                      (((lane & 7) ^ ((r >> 1) & 7)) << 4);
     }
-    const char *wg = g.w_img + (long long)bucket * g.w_grow * g.w_rowb + (size_t)bucket * g.w_gblk * 128;
+    const char *wg = BF16 ? reinterpret_cast<const char *>(g.w) + (size_t)bucket * g.gstride * 2
+                          : g.w_img + (long long)bucket * g.w_grow * g.w_rowb + (size_t)bucket * g.w_gblk * 128;
     if constexpr (!BN_LAYOUT) {
-        // W_g(n, k), k contiguous: image row = n, block = k / 32
+        // W_g(n, k), k contiguous: image row = n, block = k / 32 (bf16: row n of the weight)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int r = 8 * (wave + 4 * j) + (lane >> 3);
@@ -676,8 +753,12 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
             const int pchunk = lane & 31;
             const int seg = (pchunk >> 2) ^ (kr & 3);               // logical segment
             const int nb = min((n0 >> 5) + (seg >> 1), nblocks - 1);
-            c.b_src[j] = wg + (long long)kr * g.w_rowb + (size_t)nb * 128 + (seg & 1) * 64 +
-                         ((pchunk & 3) << 4);
+            if constexpr (BF16)     // part = seg & 1: weight row k = 32 part + kr, 32 n = 64 bytes
+                c.b_src[j] = wg + (long long)(32 * (seg & 1) + kr) * g.w_rowb + (size_t)nb * 64 +
+                             ((pchunk & 3) << 4);
+            else
+                c.b_src[j] = wg + (long long)kr * g.w_rowb + (size_t)nb * 128 + (seg & 1) * 64 +
+                             ((pchunk & 3) << 4);
         }
     }
 
@@ -692,7 +773,7 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
     // ---- k-loop: the LDS-DMAs of step t + 1 are in flight while step t is contracted; the
     // barrier at the end of a step (with the vmcnt(0) / lgkmcnt(0) hipcc puts in front of it)
     // both publishes stage (t + 1) & 1 and retires the reads of stage t & 1 ----
-    gi_stage<NI, NA, BN_LAYOUT>(c, lds0, 0);
+    gi_stage<NI, NA, BN_LAYOUT, BF16>(c, lds0, 0);
     __syncthreads();
 #ifdef GG_STAMP_DMA
     unsigned long long st[4] = {0, 0, 0, 0};
@@ -708,12 +789,12 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
 #define GG_ST
 #define GG_BAR(x) __syncthreads()
 #endif
-    for (int k0 = 0; k0 < g.K; k0 += 2 * GG_BK) {
-        gi_step<NI, NA, BN_LAYOUT, A32>(c, lds0 + GI_STAGE, lds0, k0 + GG_BK < g.K, k0 + GG_BK, acc GG_ST);
+    for (int k0 = 0; k0 < g.K; k0 += 2 * KS) {
+        gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0 + GI_STAGE, lds0, k0 + KS < g.K, k0 + KS, acc GG_ST);
         GG_BAR(0);
-        if (k0 + GG_BK < g.K) {
-            gi_step<NI, NA, BN_LAYOUT, A32>(c, lds0, lds0 + GI_STAGE, k0 + 2 * GG_BK < g.K,
-                                            k0 + 2 * GG_BK, acc GG_ST);
+        if (k0 + KS < g.K) {
+            gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0, lds0 + GI_STAGE, k0 + 2 * KS < g.K,
+                                                  k0 + 2 * KS, acc GG_ST);
             GG_BAR(0);
         }
     }
@@ -776,7 +857,7 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
 #ifdef GG_STAMP_DMA
     const unsigned long long epi0 = __builtin_amdgcn_s_memtime();
 #endif
-    gg_epilogue<NI, EPI>(g, smem, acc, bucket, row_lo, row_hi, col_tile, wm, wn, extras, EXT);
+    gg_epilogue<NI, EPI, BF16>(g, smem, acc, bucket, row_lo, row_hi, col_tile, wm, wn, extras, EXT);
 #ifdef GG_STAMP_DMA
     if (lane == 0) {
         // eight counters per wave behind the launch's output (the caller allocates the room):
@@ -1555,6 +1636,20 @@ __global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_img_kernel(Grouped
                                                            w.col_tile);
 }
 
+// spt_grouped_gemm_bf16: the image kernel's k-loop and epilogue on bf16 tensors (PLAIN / ACT / DACT)
+template <bool BN_LAYOUT, int EPI>
+__global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_bf16_kernel(GroupedArgs g) {
+    __shared__ __attribute__((aligned(1024))) float smem[GI_LDS_FLOATS + GG_EXTRAS];
+    const GgWork w = gg_find_work(g);
+    if (w.bucket < 0) return;
+    if (w.half < 0)
+        gemm_tile_img<GG_BM, BN_LAYOUT, EPI, false, false, true>(g, smem, w.bucket, w.row_lo, w.row_hi,
+                                                                 w.col_tile);
+    else
+        gemm_tile_img<GG_BM / 2, BN_LAYOUT, EPI, false, false, true>(g, smem, w.bucket, w.row_lo, w.row_hi,
+                                                                     w.col_tile);
+}
+
 // fp32 [rows, cols] (leading dimension ld) -> the bf16 image [row][cols / 32][hi | lo][32]:
 // a thread converts 8 consecutive columns (32 bytes in, 16 + 16 bytes out); columns past
 // `cols` inside the last block are zero.
@@ -1642,6 +1737,23 @@ __global__ __launch_bounds__(256) void rows_combine_kernel(
     }
 }
 
+// spt_rows_combine_bf16: the same gather-sum over bf16 rows / bias, in fp32 in the same order, one
+// rounding at the store (four columns per thread)
+__global__ __launch_bounds__(256) void rows_combine_bf16_kernel(
+    const unsigned short *__restrict__ rows, const int32_t *__restrict__ pos,
+    const unsigned short *__restrict__ bias, unsigned short *__restrict__ out, int k, int d4) {
+    const int t = blockIdx.x;
+    for (int c = threadIdx.x; c < d4; c += 256) {
+        float4 acc = bias ? gg_bf4(bias + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int j = 0; j < k; j++) {
+            const int p = pos[(size_t)t * k + j];
+            const float4 v = gg_bf4(rows + (size_t)p * d4 * 4 + 4 * c);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        *reinterpret_cast<uint2 *>(out + (size_t)t * d4 * 4 + 4 * c) =
+            make_uint2(gg_bf2_pack(acc.x, acc.y), gg_bf2_pack(acc.z, acc.w));
+    }
+}
 
 // ======================================================= weight gradient (spt_grouped_gemm_wgrad)
 // out_g(n, k) = sum over the rows p of group g of rowscale[p] G[srcG(p), n] A[srcA(p), k]: the
@@ -1705,8 +1817,12 @@ __device__ __forceinline__ void wg_put(char *t, int r, int c4, float4 v) {
     *reinterpret_cast<uint2 *>(t + r * 512 + (((seg + 1) ^ (r & 3)) << 6) + within) = make_uint2(l0, l1);
 }
 
-__global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
-    __shared__ __attribute__((aligned(16))) char smem[WG_LDS_BYTES];
+// BF16 (spt_grouped_gemm_wgrad_bf16): g, a, out and dbias hold bf16.  The rows are widened on load and
+// staged exactly as above: A's lo half is then zero and its product is left out (two MFMAs: G's hi and
+// lo parts -- G's lo is nonzero only where a rowscale multiplied it); without a rowscale every product
+// is that of the stored bf16 values, exactly
+template <bool BF16>
+__device__ __forceinline__ void wgrad_partial(WgradArgs w, char *smem) {
     int g, row0, rows;
     wg_chunk(w.offsets, w.G, w.rc, blockIdx.y, g, row0, rows);
     if (g < 0) return;                           // past the last chunk: nothing reads this slot
@@ -1720,6 +1836,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
     const bool g_ok = n0 + 4 * c4 < w.N, a_ok = k0 + 4 * c4 < w.K;
     const float *gp = w.g + n0 + 4 * c4;
     const float *ap = w.a + k0 + 4 * c4;
+    const unsigned short *gpb = reinterpret_cast<const unsigned short *>(w.g) + n0 + 4 * c4;
+    const unsigned short *apb = reinterpret_cast<const unsigned short *>(w.a) + k0 + 4 * c4;
     const bool want_bias = w.pbias && kt == 0;
     float4 bias_acc = make_float4(0.f, 0.f, 0.f, 0.f);
     // the source rows and scales of a step are fetched one step ahead of its data
@@ -1739,10 +1857,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const bool in = p0 + rs + 8 * j < rows;
-            vg[j] = in && g_ok ? *reinterpret_cast<const float4 *>(gp + (long long)ig[j] * w.ldg)
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
-            va[j] = in && a_ok ? *reinterpret_cast<const float4 *>(ap + (long long)ia[j] * w.lda)
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (BF16) {
+                vg[j] = in && g_ok ? gg_bf4(gpb + (long long)ig[j] * w.ldg) : make_float4(0.f, 0.f, 0.f, 0.f);
+                va[j] = in && a_ok ? gg_bf4(apb + (long long)ia[j] * w.lda) : make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                vg[j] = in && g_ok ? *reinterpret_cast<const float4 *>(gp + (long long)ig[j] * w.ldg)
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+                va[j] = in && a_ok ? *reinterpret_cast<const float4 *>(ap + (long long)ia[j] * w.lda)
+                                   : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
             sv[j] = sn[j];
         }
     };
@@ -1790,7 +1913,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j] = gg_mma3(fa[i], fb[j], acc[i][j]);
+                for (int j = 0; j < 2; j++) {
+                    if constexpr (BF16) {
+                        acc[i][j] = gg_mma(fa[i].lo, fb[j].hi, acc[i][j]);
+                        acc[i][j] = gg_mma(fa[i].hi, fb[j].hi, acc[i][j]);
+                    } else {
+                        acc[i][j] = gg_mma3(fa[i], fb[j], acc[i][j]);
+                    }
+                }
         }
     }
     // acc[i][j][r] = C[n = wm + 32 i + (r & 3) + 8 (r >> 2) + 4 fh][k = wn + 32 j + (lane & 31)]
@@ -1824,9 +1954,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
     }
 }
 
+__global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(WgradArgs w) {
+    __shared__ __attribute__((aligned(16))) char smem[WG_LDS_BYTES];
+    wgrad_partial<false>(w, smem);
+}
+
+__global__ __launch_bounds__(256, 2) void wgrad_partial_bf16_kernel(WgradArgs w) {
+    __shared__ __attribute__((aligned(16))) char smem[WG_LDS_BYTES];
+    wgrad_partial<true>(w, smem);
+}
+
 // out_g = the sum of group g's chunk partials in chunk order (zero for a group without rows);
 // elements N K .. N K + N - 1 of the index space are dbias.  A thread per four elements.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradArgs w) {
+template <bool BF16>
+__device__ __forceinline__ void wgrad_reduce(WgradArgs w) {
     const int g = blockIdx.y;
     const long long nk = (long long)w.N * w.K;
     const long long e = 4 * ((long long)blockIdx.x * 256 + threadIdx.x);
@@ -1850,13 +1991,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradArgs w) {
         const float4 u = *reinterpret_cast<const float4 *>(src + (size_t)c * step);
         t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
     }
-    if (bias) {
+    if (BF16) {         // the one rounding of the bf16 parameter layout
+        const uint2 v = make_uint2(gg_bf2_pack(t.x, t.y), gg_bf2_pack(t.z, t.w));
+        const long long n = e / w.K, k = e - n * w.K;
+        unsigned short *dst = bias ? reinterpret_cast<unsigned short *>(w.dbias) + (size_t)g * w.N + (e - nk)
+                                   : reinterpret_cast<unsigned short *>(w.out) + g * w.gstride + n * w.ldn + k;
+        *reinterpret_cast<uint2 *>(dst) = v;
+    } else if (bias) {
         *reinterpret_cast<float4 *>(w.dbias + (size_t)g * w.N + (e - nk)) = t;
     } else {
         const long long n = e / w.K, k = e - n * w.K;
         *reinterpret_cast<float4 *>(w.out + g * w.gstride + n * w.ldn + k) = t;
     }
 }
+
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradArgs w) { wgrad_reduce<false>(w); }
+__global__ __launch_bounds__(256) void wgrad_reduce_bf16_kernel(WgradArgs w) { wgrad_reduce<true>(w); }
 
 }  // namespace spt
 
@@ -2142,19 +2292,20 @@ extern "C" long long spt_grouped_gemm_wgrad_workspace_bytes(long long n_rows, in
     return wgrad_chunks(n_rows, n_groups) * ((long long)n * k + n) * (long long)sizeof(float);
 }
 
-extern "C" int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32_t *gather_g,
-                                      const float *a, long long lda, const int32_t *gather_a,
-                                      const float *rowscale, const int32_t *offsets, int n_groups,
-                                      long long n_rows, int n, int k, float *out,
-                                      long long group_stride, long long ldn, float *dbias,
-                                      void *workspace, void *stream) {
+// both element types: the validation, the chunking and the two launches are the same
+static int launch_wgrad(bool bf16, const void *g, long long ldg, const int32_t *gather_g, const void *a,
+                        long long lda, const int32_t *gather_a, const float *rowscale, const int32_t *offsets,
+                        int n_groups, long long n_rows, int n, int k, void *out, long long group_stride,
+                        long long ldn, void *dbias, void *workspace, void *stream) {
     if (!g || !a || !offsets || !out || !workspace) return SPT_EINVAL;
     if (n_groups < 1 || n_rows < 0 || n <= 0 || k <= 0 || ldg < n || lda < k || ldn < k || group_stride < 0)
         return SPT_EINVAL;
     if (n % 4 != 0 || k % 4 != 0 || ldg % 4 != 0 || lda % 4 != 0 || ldn % 4 != 0 || group_stride % 4 != 0)
         return SPT_ESHAPE;
-    if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(out) |
-          reinterpret_cast<uintptr_t>(dbias) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0)
+    // four elements per access: 16 bytes of fp32, 8 of bf16; the fp32 partials in the workspace: 16
+    const uintptr_t operands = reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(a) |
+                               reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dbias);
+    if ((operands & (bf16 ? 7 : 15)) != 0 || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
         return SPT_ESHAPE;
     const long long chunks = wgrad_chunks(n_rows, n_groups);
     const long long tiles = (long long)((n + WG_T - 1) / WG_T) * ((k + WG_T - 1) / WG_T);
@@ -2162,8 +2313,9 @@ extern "C" int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32
         ((long long)n * k + n + 3) / 4 / 256 + 1 > 0x7FFFFFFFll)
         return SPT_EUNSUP;
     WgradArgs w = {};
-    w.g = g; w.a = a; w.gather_g = gather_g; w.gather_a = gather_a; w.rowscale = rowscale;
-    w.offsets = offsets; w.out = out; w.dbias = dbias;
+    w.g = static_cast<const float *>(g); w.a = static_cast<const float *>(a);
+    w.gather_g = gather_g; w.gather_a = gather_a; w.rowscale = rowscale;
+    w.offsets = offsets; w.out = static_cast<float *>(out); w.dbias = static_cast<float *>(dbias);
     w.partial = static_cast<float *>(workspace);
     w.pbias = dbias ? w.partial + chunks * n * (long long)k : nullptr;
     w.ldg = ldg; w.lda = lda; w.gstride = group_stride; w.ldn = ldn;
@@ -2171,12 +2323,115 @@ extern "C" int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32
     w.rc = (int)wgrad_rows_per_chunk(n_rows);
     hipStream_t s = (hipStream_t)stream;
     if (n_rows > 0) {
-        hipLaunchKernelGGL(wgrad_partial_kernel, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, w);
+        hipLaunchKernelGGL(bf16 ? wgrad_partial_bf16_kernel : wgrad_partial_kernel,
+                           dim3((unsigned)tiles, (unsigned)chunks), dim3(256), 0, s, w);
         SPT_LAUNCH_CHECK();
     }
     const long long elems = (long long)n * k + (dbias ? n : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((elems / 4 + 255) / 256), (unsigned)n_groups),
-                       dim3(256), 0, s, w);
+    hipLaunchKernelGGL(bf16 ? wgrad_reduce_bf16_kernel : wgrad_reduce_kernel,
+                       dim3((unsigned)((elems / 4 + 255) / 256), (unsigned)n_groups), dim3(256), 0, s, w);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_grouped_gemm_wgrad(const float *g, long long ldg, const int32_t *gather_g,
+                                      const float *a, long long lda, const int32_t *gather_a,
+                                      const float *rowscale, const int32_t *offsets, int n_groups,
+                                      long long n_rows, int n, int k, float *out,
+                                      long long group_stride, long long ldn, float *dbias,
+                                      void *workspace, void *stream) {
+    return launch_wgrad(false, g, ldg, gather_g, a, lda, gather_a, rowscale, offsets, n_groups, n_rows, n, k,
+                        out, group_stride, ldn, dbias, workspace, stream);
+}
+
+// ---- the bf16 entries ----
+// the partials stay fp32: the same workspace as spt_grouped_gemm_wgrad
+extern "C" long long spt_grouped_gemm_wgrad_bf16_workspace_bytes(long long n_rows, int n_groups, int n, int k) {
+    return spt_grouped_gemm_wgrad_workspace_bytes(n_rows, n_groups, n, k);
+}
+
+extern "C" int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const int32_t *gather_g,
+                                           const void *a, long long lda, const int32_t *gather_a,
+                                           const float *rowscale, const int32_t *offsets, int n_groups,
+                                           long long n_rows, int n, int k, void *out,
+                                           long long group_stride, long long ldn, void *dbias,
+                                           void *workspace, void *stream) {
+    return launch_wgrad(true, g, ldg, gather_g, a, lda, gather_a, rowscale, offsets, n_groups, n_rows, n, k,
+                        out, group_stride, ldn, dbias, workspace, stream);
+}
+
+extern "C" int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *d, void *stream) {
+    if (!d) return SPT_EINVAL;
+    if (!d->a || !d->w || !d->offsets || !d->out) return SPT_EINVAL;
+    if (d->n_rows <= 0 || d->k <= 0 || d->n <= 0 || d->n_groups <= 0 || d->lda < d->k) return SPT_EINVAL;
+    const int epilogue = d->epilogue;
+    if (epilogue < EPI_PLAIN || epilogue > EPI_DACT) return SPT_EINVAL;
+    if (epilogue != EPI_PLAIN && (d->activation < ACT_RELU || d->activation > ACT_SILU)) return SPT_EUNSUP;
+    if (d->accumulate && epilogue != EPI_PLAIN) return SPT_EUNSUP;
+    const long long ldo = d->ldo == 0 ? d->n : d->ldo;
+    if (ldo < d->n || d->w_group_stride < 0) return SPT_EINVAL;
+    if (d->w_ldk != 1 && d->w_ldn != 1) return SPT_EUNSUP;
+    // LDS-DMA moves 16 bytes per lane: 16-byte aligned rows of both operands; a stage is 64 k
+    const auto misaligned = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (d->k % (2 * GG_BK) != 0 || d->lda % 8 != 0 || d->w_group_stride % 8 != 0) return SPT_ESHAPE;
+    if (misaligned(d->a, 15) || misaligned(d->w, 15)) return SPT_ESHAPE;
+    if (d->w_ldk == 1 && (d->w_ldn < d->k || d->w_ldn % 8 != 0)) return SPT_ESHAPE;
+    if (d->w_ldk != 1 && (d->w_ldk < d->n || d->w_ldk % 8 != 0 || d->n % 32 != 0)) return SPT_ESHAPE;
+    // the epilogue's 4-column pieces: 8-byte aligned bf16 tensors
+    if (misaligned(d->out, 7) || misaligned(d->out2, 7) || misaligned(d->bias, 7) || misaligned(d->h_in, 7) ||
+        misaligned(d->s_in, 7))
+        return SPT_ESHAPE;
+    const unsigned row_tiles = (unsigned)((d->n_rows + GG_BM - 1) / GG_BM + d->n_groups);
+    const unsigned col_tiles = (unsigned)((d->n + GG_BN - 1) / GG_BN);
+    if ((unsigned long long)row_tiles * col_tiles > 0x3FFFFFFFull) return SPT_EUNSUP;
+    if (epilogue == EPI_DACT) {
+        if (!d->h_in && !d->s_in) return SPT_EINVAL;
+        if (!d->s_in && d->activation != ACT_RELU) return SPT_EINVAL;   // only ReLU is a function of h
+        if (!d->pdot_main != !d->pdot_act) return SPT_EINVAL;
+        if (d->pdot_main && d->pdot_ld < (int)(2 * col_tiles)) return SPT_ESHAPE;
+    }
+    GroupedArgs g = {};
+    // (the bf16 tensors travel in GroupedArgs' float pointers; the kernel reads them as bf16)
+    g.a = static_cast<const float *>(d->a); g.gather = d->gather; g.w = static_cast<const float *>(d->w);
+    g.bias = static_cast<const float *>(d->bias); g.rowscale = d->rowscale;
+    g.offsets = d->offsets; g.out = static_cast<float *>(d->out);
+    g.P = d->n_rows; g.K = d->k; g.N = d->n; g.G = d->n_groups; g.lda = d->lda;
+    g.gstride = d->w_group_stride; g.ldn = d->w_ldn; g.ldk = d->w_ldk;
+    g.ldo = ldo; g.accumulate = d->accumulate;
+    g.act = d->activation; g.out2 = static_cast<float *>(d->out2);
+    g.h_in = static_cast<const float *>(d->h_in); g.s_in = static_cast<const float *>(d->s_in);
+    g.pdot_main = d->pdot_main; g.pdot_act = d->pdot_act; g.pdot_ld = d->pdot_ld;
+    g.a_rowb = (long long)d->lda * 2;
+    g.w_rowb = (long long)(d->w_ldk == 1 ? d->w_ldn : d->w_ldk) * 2;
+    g.slots = resident_slots();
+    if (g.slots <= 0) return SPT_EINVAL;
+    const dim3 grid(2 * row_tiles * col_tiles);
+    hipStream_t s = (hipStream_t)stream;
+#define SPT_GB(BN)                                                                                         \
+    do {                                                                                                   \
+        if (epilogue == EPI_PLAIN)                                                                         \
+            hipLaunchKernelGGL((grouped_gemm_bf16_kernel<BN, EPI_PLAIN>), grid, dim3(GG_THREADS), 0, s, g); \
+        else if (epilogue == EPI_ACT)                                                                      \
+            hipLaunchKernelGGL((grouped_gemm_bf16_kernel<BN, EPI_ACT>), grid, dim3(GG_THREADS), 0, s, g);   \
+        else                                                                                               \
+            hipLaunchKernelGGL((grouped_gemm_bf16_kernel<BN, EPI_DACT>), grid, dim3(GG_THREADS), 0, s, g);  \
+    } while (0)
+    if (d->w_ldk == 1) SPT_GB(false); else SPT_GB(true);
+#undef SPT_GB
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_rows_combine_bf16(const void *rows, const int32_t *pos, const void *bias, void *out,
+                                     int n_tokens, int k, int d, void *stream) {
+    if (!rows || !pos || !out) return SPT_EINVAL;
+    if (n_tokens <= 0 || k <= 0 || d <= 0) return SPT_EINVAL;
+    if (d % 4 != 0 || ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(bias) |
+                        reinterpret_cast<uintptr_t>(out)) & 7) != 0)
+        return SPT_ESHAPE;
+    hipLaunchKernelGGL(rows_combine_bf16_kernel, dim3((unsigned)n_tokens), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const unsigned short *>(rows), pos, static_cast<const unsigned short *>(bias),
+                       static_cast<unsigned short *>(out), k, d / 4);
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }

@@ -17,6 +17,7 @@
 // ties to the lower block index (a total order; torch.topk leaves ties unspecified).  G <= 8, T <= 65536 (64 tokens per thread); bigger
 // problems use the torch composition (layers/sparse/grouped.py).
 #include "spt_common.h"
+#include <initializer_list>
 
 namespace spt {
 
@@ -405,6 +406,80 @@ extern "C" int spt_swiglu_backward(const float *grad_h, const float *gate, const
         return SPT_ESHAPE;
     hipLaunchKernelGGL(swiglu_backward_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
                        (hipStream_t)stream, grad_h, gate, side, grad_gate, grad_side, dots, rows, n);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+// ---- bf16 storage (spt_swiglu_forward_bf16 / _backward_bf16): four elements per thread, widened
+// exactly, computed in fp32 as above, each result rounded once (RNE) ----
+typedef __attribute__((ext_vector_type(2))) __bf16 sw_bf16x2;
+typedef __attribute__((ext_vector_type(2))) float sw_f32x2;
+__device__ __forceinline__ float4 sw_load4(const unsigned short *p) {
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__builtin_bit_cast(float, v.x << 16), __builtin_bit_cast(float, v.x & 0xffff0000u),
+                       __builtin_bit_cast(float, v.y << 16), __builtin_bit_cast(float, v.y & 0xffff0000u));
+}
+__device__ __forceinline__ void sw_store4(unsigned short *p, float a, float b, float c, float d) {
+    const sw_f32x2 x = {a, b}, y = {c, d};
+    *reinterpret_cast<uint2 *>(p) = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(x, sw_bf16x2)),
+                                               __builtin_bit_cast(unsigned, __builtin_convertvector(y, sw_bf16x2)));
+}
+
+__global__ __launch_bounds__(256) void swiglu_forward_bf16_kernel(const unsigned short *__restrict__ g,
+                                                                  const unsigned short *__restrict__ s,
+                                                                  unsigned short *__restrict__ h, long long n4) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const float4 a = sw_load4(g + 4 * i), b = sw_load4(s + 4 * i);
+        sw_store4(h + 4 * i, silu_f(a.x) * b.x, silu_f(a.y) * b.y, silu_f(a.z) * b.z, silu_f(a.w) * b.w);
+    }
+}
+
+__global__ __launch_bounds__(256) void swiglu_backward_bf16_kernel(
+    const unsigned short *__restrict__ dh, const unsigned short *__restrict__ g,
+    const unsigned short *__restrict__ s, unsigned short *__restrict__ dg, unsigned short *__restrict__ ds,
+    long long n4) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const float4 vdh = sw_load4(dh + 4 * i), vg = sw_load4(g + 4 * i), vs = sw_load4(s + 4 * i);
+        const float xdh[4] = {vdh.x, vdh.y, vdh.z, vdh.w}, xg[4] = {vg.x, vg.y, vg.z, vg.w},
+                    xs[4] = {vs.x, vs.y, vs.z, vs.w};
+        float og[4], os[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            os[e] = xdh[e] * silu_f(xg[e]);
+            og[e] = xdh[e] * xs[e] * silu_grad_f(xg[e]);
+        }
+        sw_store4(dg + 4 * i, og[0], og[1], og[2], og[3]);
+        sw_store4(ds + 4 * i, os[0], os[1], os[2], os[3]);
+    }
+}
+
+static bool sw_bf16_args(long long n_elements, std::initializer_list<const void *> ptrs) {
+    uintptr_t any = 0;
+    for (const void *p : ptrs) any |= reinterpret_cast<uintptr_t>(p);
+    return n_elements % 4 == 0 && (any & 7) == 0;
+}
+
+extern "C" int spt_swiglu_forward_bf16(const void *gate, const void *side, void *h, long long n_elements,
+                                       void *stream) {
+    if (!gate || !side || !h || n_elements <= 0) return SPT_EINVAL;
+    if (!sw_bf16_args(n_elements, {gate, side, h})) return SPT_ESHAPE;
+    const long long n4 = n_elements / 4, blocks = (n4 + 255) / 256;
+    hipLaunchKernelGGL(swiglu_forward_bf16_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0,
+                       (hipStream_t)stream, static_cast<const unsigned short *>(gate),
+                       static_cast<const unsigned short *>(side), static_cast<unsigned short *>(h), n4);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_swiglu_backward_bf16(const void *grad_h, const void *gate, const void *side, void *grad_gate,
+                                        void *grad_side, long long n_elements, void *stream) {
+    if (!grad_h || !gate || !side || !grad_gate || !grad_side || n_elements <= 0) return SPT_EINVAL;
+    if (!sw_bf16_args(n_elements, {grad_h, gate, side, grad_gate, grad_side})) return SPT_ESHAPE;
+    const long long n4 = n_elements / 4, blocks = (n4 + 255) / 256;
+    hipLaunchKernelGGL(swiglu_backward_bf16_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256),
+                       0, (hipStream_t)stream, static_cast<const unsigned short *>(grad_h),
+                       static_cast<const unsigned short *>(gate), static_cast<const unsigned short *>(side),
+                       static_cast<unsigned short *>(grad_gate), static_cast<unsigned short *>(grad_side), n4);
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }

@@ -79,17 +79,25 @@ _PROTOTYPES = {
     'spt_grouped_gemm_wgrad': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, ctypes.c_longlong] + [_c_ptr] * 3
                                + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
                                   ctypes.c_longlong] + [_c_ptr] * 3, _c_int),
+    'spt_grouped_gemm_bf16': ([_c_ptr, _c_ptr], _c_int),
+    'spt_grouped_gemm_wgrad_bf16_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
+    'spt_grouped_gemm_wgrad_bf16': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, ctypes.c_longlong] + [_c_ptr] * 3
+                                    + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
+                                       ctypes.c_longlong] + [_c_ptr] * 3, _c_int),
     'spt_split_bf16_bytes': ([ctypes.c_longlong, _c_int], ctypes.c_size_t),
     'spt_split_bf16': ([_c_ptr, _c_ptr, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_ptr], _c_int),
     'spt_rotary': ([_c_ptr, _c_int, _c_int, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr] + [_c_int] * 5 + [_c_ptr],
                    _c_int),
     'spt_swiglu_forward': ([_c_ptr] * 3 + [ctypes.c_longlong, _c_ptr], _c_int),
     'spt_swiglu_backward': ([_c_ptr] * 6 + [ctypes.c_longlong, _c_int, _c_ptr], _c_int),
+    'spt_swiglu_forward_bf16': ([_c_ptr] * 3 + [ctypes.c_longlong, _c_ptr], _c_int),
+    'spt_swiglu_backward_bf16': ([_c_ptr] * 5 + [ctypes.c_longlong, _c_ptr], _c_int),
     'spt_embedding_rows_backward_workspace_bytes': ([ctypes.c_longlong, _c_int], ctypes.c_longlong),
     'spt_embedding_rows_backward': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, _c_ptr, ctypes.c_longlong, _c_ptr,
                                      ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_ptr], _c_int),
     'spt_rows_combine': ([_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_rows_combine_side': ([_c_ptr] * 5 + [_c_int, _c_ptr] + [_c_int] * 3 + [_c_ptr], _c_int),
+    'spt_rows_combine_bf16': ([_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_ffn_coeff_grad': ([_c_ptr, _c_ptr, _c_int] + [_c_ptr] * 6 + [_c_f32, _c_ptr, _c_int, _c_int, _c_ptr],
                            _c_int),
     'spt_layernorm_partial_rows': ([ctypes.c_longlong], _c_int),
@@ -962,7 +970,11 @@ def grouped_gemm(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Tensor,
     """Token-bucketed grouped GEMM (``spt_grouped_gemm``): for the rows of bucket g,
     ``out = rowscale * (a[gather] @ W_g^T + bias[g])`` with
     ``W_g(n, k) = weight.flatten()[g * w_group_stride + n * w_ldn + k * w_ldk]``.
-    ``offsets`` [n_groups + 1] int32 stays on the device."""
+    ``offsets`` [n_groups + 1] int32 stays on the device.  bf16 ``a`` and ``weight`` (and bias) take
+    ``spt_grouped_gemm_bf16`` and give bf16 rows; a mix of bf16 and fp32 operands is refused."""
+    if _bf16_operands('grouped_gemm', a=a, weight=weight, bias=bias):
+        return grouped_gemm_bf16(a, weight, offsets, n_groups, n, k, w_group_stride, w_ldn, w_ldk,
+                                 n_rows=n_rows, gather=gather, bias=bias, rowscale=rowscale)
     _check_type(a, torch.float32, 'a')
     _check_type(weight, torch.float32, 'weight')
     _check_type(offsets, torch.int32, 'offsets')
@@ -1006,12 +1018,15 @@ def grouped_gemm_wgrad(grad: torch.Tensor, a: torch.Tensor, offsets: torch.Tenso
     ``want_bias`` ``dbias[g, n] = sum_p rowscale[p] grad[gather_grad[p], n]``.  Every element of
     ``out`` that a group addresses is written (zeros for an empty group).  -> (out, dbias | None);
     ``out`` defaults to a new contiguous tensor over the view's extent (zeros where no group reaches:
-    none for the routed FFN's fc1 / fc2 views, which tile their weights exactly)."""
+    none for the routed FFN's fc1 / fc2 views, which tile their weights exactly).  bf16 ``grad`` and ``a``
+    take ``spt_grouped_gemm_wgrad_bf16``: ``out`` and dbias are bf16 then (fp32 inside, rounded once)."""
     n, k, gstride, ldn, ldk = view
+    bf16 = _bf16_operands('grouped_gemm_wgrad', grad=grad, a=a, out=out)
+    dtype = torch.bfloat16 if bf16 else torch.float32
     _require(ldk == 1, 'grouped_gemm_wgrad: k-contiguous views only (ldk == 1)')
     n_groups = offsets.numel() - 1
     for t, name in ((grad, 'grad'), (a, 'a')):
-        _check_type(t, torch.float32, name)
+        _check_type(t, dtype, name)
         _require(t.is_cuda and t.dim() == 2 and t.stride(1) == 1, name + ': CUDA [rows, cols], unit inner stride')
     _require(grad.size(1) == n and a.size(1) == k, 'grouped_gemm_wgrad: grad [*, n], a [*, k]')
     _check_type(offsets, torch.int32, 'offsets')
@@ -1033,20 +1048,111 @@ def grouped_gemm_wgrad(grad: torch.Tensor, a: torch.Tensor, offsets: torch.Tenso
         extent = (n_groups - 1) * gstride + (n - 1) * ldn + k
         if out is None:
             alloc = torch.empty if n_groups * n * k == extent else torch.zeros
-            out = alloc([extent], dtype=torch.float32, device=dev)
-        _check_type(out, torch.float32, 'out')
+            out = alloc([extent], dtype=dtype, device=dev)
+        _check_type(out, dtype, 'out')
         _require(out.is_contiguous() and out.device == dev, 'out: contiguous on the device of grad')
         _require(out.numel() >= extent, 'out: too small for the view')
-        dbias = torch.empty([n_groups, n], dtype=torch.float32, device=dev) if want_bias else None
-        work = torch.empty([lib.spt_grouped_gemm_wgrad_workspace_bytes(n_rows, n_groups, n, k)],
-                           dtype=torch.uint8, device=dev)
-        rc = lib.spt_grouped_gemm_wgrad(grad.data_ptr(), grad.stride(0), _ptr(gather_grad),
+        dbias = torch.empty([n_groups, n], dtype=dtype, device=dev) if want_bias else None
+        bytes_fn = lib.spt_grouped_gemm_wgrad_bf16_workspace_bytes if bf16 else lib.spt_grouped_gemm_wgrad_workspace_bytes
+        work = torch.empty([bytes_fn(n_rows, n_groups, n, k)], dtype=torch.uint8, device=dev)
+        entry = lib.spt_grouped_gemm_wgrad_bf16 if bf16 else lib.spt_grouped_gemm_wgrad
+        rc = entry(grad.data_ptr(), grad.stride(0), _ptr(gather_grad),
                                         a.data_ptr(), a.stride(0), _ptr(gather_a), _ptr(rowscale),
                                         offsets.data_ptr(), n_groups, n_rows, n, k, out.data_ptr(),
                                         gstride, ldn, _ptr(dbias), work.data_ptr(), _stream(dev))
     if rc != 0:
         _raise(lib, rc, 'grouped_gemm_wgrad')
     return out, dbias
+
+
+def _bf16_operands(what: str, **tensors) -> bool:
+    """True when the given tensors (None: absent) are all bf16, False when none is; a mix of bf16
+    and other dtypes is an error (no silent conversion)."""
+    given = {k: t for k, t in tensors.items() if t is not None}
+    is_bf16 = [t.dtype == torch.bfloat16 for t in given.values()]
+    if any(is_bf16) and not all(is_bf16):
+        raise RuntimeError('{}: mixed dtypes ({}): bf16 operands take the bf16 kernels only together'.format(
+            what, ', '.join('{} {}'.format(k, t.dtype) for k, t in given.items())))
+    return any(is_bf16)
+
+
+class _GroupedDescBf16(ctypes.Structure):
+    """``SptGroupedGemmBf16`` of include/spt_hip.h."""
+    _fields_ = [
+        ('a', _c_ptr), ('gather', _c_ptr), ('w', _c_ptr), ('bias', _c_ptr),
+        ('rowscale', _c_ptr), ('offsets', _c_ptr), ('out', _c_ptr),
+        ('n_rows', ctypes.c_int32), ('k', ctypes.c_int32), ('n', ctypes.c_int32),
+        ('n_groups', ctypes.c_int32), ('lda', ctypes.c_int32),
+        ('w_group_stride', ctypes.c_int64), ('w_ldn', ctypes.c_int32), ('w_ldk', ctypes.c_int32),
+        ('ldo', ctypes.c_int64), ('epilogue', ctypes.c_int32), ('activation', ctypes.c_int32),
+        ('accumulate', ctypes.c_int32), ('out2', _c_ptr), ('h_in', _c_ptr), ('s_in', _c_ptr),
+        ('pdot_main', _c_ptr), ('pdot_act', _c_ptr), ('pdot_ld', ctypes.c_int32),
+    ]
+
+
+def grouped_gemm_bf16_supported(k: int, n: int, w_group_stride: int, w_ldn: int, w_ldk: int, lda: int) -> bool:
+    """The shapes ``spt_grouped_gemm_bf16`` takes (include/spt_hip.h; pointers 16-byte aligned)."""
+    if k % 64 or lda % 8 or w_group_stride % 8:
+        return False
+    if w_ldk == 1:
+        return w_ldn % 8 == 0 and w_ldn >= k
+    return w_ldn == 1 and w_ldk % 8 == 0 and w_ldk >= n and n % 32 == 0
+
+
+def grouped_gemm_bf16(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Tensor,
+                      n_groups: int, n: int, k: int, w_group_stride: int, w_ldn: int, w_ldk: int,
+                      n_rows: int = None, gather=None, bias=None, rowscale=None,
+                      epilogue: int = 0, activation: int = 0, keep_preact: bool = False,
+                      h_in=None, s_in=None, out: torch.Tensor = None, accumulate: bool = False):
+    """``spt_grouped_gemm_bf16``: the grouped GEMM of ``grouped_gemm`` / ``grouped_gemm_fused`` on bf16
+    storage -- fp32 accumulation of the exact products of the bf16 values, one rounding per stored
+    value.  ``bias``, ``h_in``, ``s_in``, ``out`` bf16; ``rowscale`` fp32.  Returns ``out`` (EPI_PLAIN,
+    EPI_DACT) or ``(out, preact | None)`` (EPI_ACT)."""
+    for t, name in ((a, 'a'), (weight, 'weight')):
+        _check_type(t, torch.bfloat16, name)
+    _check_type(offsets, torch.int32, 'offsets')
+    _require(a.is_cuda and weight.is_cuda and offsets.is_cuda, 'grouped_gemm_bf16 needs CUDA tensors')
+    _require(a.dim() == 2 and a.stride(1) == 1, 'a must be [rows, k] with unit inner stride')
+    _require(weight.is_contiguous(), 'weight must be contiguous')
+    _require(offsets.numel() == n_groups + 1, 'offsets must have n_groups + 1 entries')
+    dev = _same_device(a, weight, offsets)
+    if n_rows is None:
+        n_rows = gather.numel() if gather is not None else a.size(0)
+    if gather is not None:
+        _check_type(gather, torch.int32, 'gather')
+    for t, name, dt in ((bias, 'bias', torch.bfloat16), (rowscale, 'rowscale', torch.float32),
+                        (h_in, 'h_in', torch.bfloat16), (s_in, 's_in', torch.bfloat16)):
+        if t is not None:
+            _check_type(t, dt, name)
+            _require(t.is_cuda and t.is_contiguous(), name + ' must be a contiguous CUDA tensor')
+    _require(grouped_gemm_bf16_supported(k, n, w_group_stride, w_ldn, w_ldk, a.stride(0))
+             and a.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0,
+             'grouped_gemm_bf16: k % 64 == 0, 16-byte aligned rows of a and of the weight (include/spt_hip.h)')
+    lib = load_library()
+    with _on(dev):
+        _require(not accumulate or out is not None, 'accumulate: needs `out`')
+        if out is None:
+            out = torch.empty([n_rows, n], dtype=torch.bfloat16, device=dev)
+        else:
+            _check_type(out, torch.bfloat16, 'out')
+            _require(epilogue == EPI_PLAIN and out.is_cuda and out.dim() == 2 and out.stride(1) == 1
+                     and out.size(0) == n_rows and out.size(1) >= n,
+                     'out: [n_rows, >= n] bf16 with unit inner stride (EPI_PLAIN only)')
+        preact = torch.empty_like(out) if epilogue == EPI_ACT and keep_preact else None
+        if n_rows > 0:
+            desc = _GroupedDescBf16(
+                a=_ptr(a), gather=_ptr(gather), w=_ptr(weight), bias=_ptr(bias), rowscale=_ptr(rowscale),
+                offsets=_ptr(offsets), out=_ptr(out), n_rows=n_rows, k=k, n=n, n_groups=n_groups,
+                lda=a.stride(0), w_group_stride=w_group_stride, w_ldn=w_ldn, w_ldk=w_ldk, ldo=out.stride(0),
+                epilogue=epilogue, activation=activation, accumulate=int(bool(accumulate)),
+                out2=_ptr(preact), h_in=_ptr(h_in), s_in=_ptr(s_in), pdot_main=None, pdot_act=None, pdot_ld=0)
+            PATH_COUNTS[('grouped_gemm', 'bf16')] += 1
+            rc = lib.spt_grouped_gemm_bf16(ctypes.byref(desc), _stream(dev))
+            if rc != 0:
+                _raise(lib, rc, 'grouped_gemm_bf16')
+    if epilogue == EPI_ACT:
+        return out, preact
+    return out
 
 
 class _GroupedDesc(ctypes.Structure):
@@ -1591,6 +1697,41 @@ def swiglu_supported(g: torch.Tensor, s: torch.Tensor) -> bool:
             and g.data_ptr() % 16 == 0 and s.data_ptr() % 16 == 0)
 
 
+def swiglu_bf16_supported(g: torch.Tensor, s: torch.Tensor) -> bool:
+    return (g.is_cuda and g.dtype == s.dtype == torch.bfloat16 and g.shape == s.shape and g.is_contiguous()
+            and s.is_contiguous() and g.numel() % 4 == 0 and g.numel() > 0
+            and g.data_ptr() % 8 == 0 and s.data_ptr() % 8 == 0)
+
+
+def swiglu_forward_bf16(g: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """``spt_swiglu_forward_bf16``: silu(g) * s on bf16, fp32 inside, rounded once."""
+    _require(swiglu_bf16_supported(g, s), 'swiglu_bf16: contiguous bf16 CUDA pair, numel % 4 == 0')
+    dev = g.device
+    lib = load_library()
+    with _on(dev):
+        h = torch.empty_like(g)
+        rc = lib.spt_swiglu_forward_bf16(g.data_ptr(), s.data_ptr(), h.data_ptr(), g.numel(), _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'swiglu_forward_bf16')
+    return h
+
+
+def swiglu_backward_bf16(dh: torch.Tensor, g: torch.Tensor, s: torch.Tensor):
+    """``spt_swiglu_backward_bf16``: -> (dg, ds) on bf16 (no row dots)."""
+    _require(swiglu_bf16_supported(g, s) and dh.shape == g.shape and dh.dtype == torch.bfloat16
+             and dh.is_contiguous() and dh.device == g.device and dh.data_ptr() % 8 == 0,
+             'swiglu_bf16: contiguous bf16 CUDA tensors, numel % 4 == 0')
+    dev = g.device
+    lib = load_library()
+    with _on(dev):
+        dg, ds = torch.empty_like(g), torch.empty_like(g)
+        rc = lib.spt_swiglu_backward_bf16(dh.data_ptr(), g.data_ptr(), s.data_ptr(), dg.data_ptr(), ds.data_ptr(),
+                                          g.numel(), _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'swiglu_backward_bf16')
+    return dg, ds
+
+
 def swiglu_forward(g: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     """``spt_swiglu_forward``: silu(g) * s."""
     _require(swiglu_supported(g, s), 'swiglu: contiguous fp32 CUDA [rows, n % 4 == 0] pair')
@@ -1649,7 +1790,10 @@ def embedding_rows_backward(grad: torch.Tensor, ids: torch.Tensor, n_rows: int) 
 def rows_combine(rows: torch.Tensor, pos: torch.Tensor, bias: torch.Tensor = None,
                  side: torch.Tensor = None, side_weight: torch.Tensor = None) -> torch.Tensor:
     """out[t] = bias + sum_j rows[pos[t, j]] (``spt_rows_combine``); pos [T, k] int32.  With ``side``
-    [T, ns] and ``side_weight`` [ns, d] (``spt_rows_combine_side``) side @ side_weight is added on top."""
+    [T, ns] and ``side_weight`` [ns, d] (``spt_rows_combine_side``) side @ side_weight is added on top.
+    bf16 ``rows`` (and bias) take ``spt_rows_combine_bf16`` (no side): summed in fp32, rounded once."""
+    if _bf16_operands('rows_combine', rows=rows, bias=bias):
+        return _rows_combine_bf16(rows, pos, bias, side)
     _check_type(rows, torch.float32, 'rows')
     _check_type(pos, torch.int32, 'pos')
     _require(rows.dim() == 2 and rows.is_contiguous() and pos.dim() == 2 and pos.is_contiguous(),
@@ -1991,3 +2135,24 @@ def softmax_backward_clamped(indptr: torch.Tensor, indices: torch.Tensor,
     if rc != 0:
         _raise(lib, rc, 'softmax_backward_clamped')
     return grad
+
+
+def _rows_combine_bf16(rows: torch.Tensor, pos: torch.Tensor, bias, side) -> torch.Tensor:
+    _check_type(pos, torch.int32, 'pos')
+    _require(side is None, 'rows_combine: no side product on bf16 rows')
+    _require(rows.dim() == 2 and rows.is_contiguous() and pos.dim() == 2 and pos.is_contiguous()
+             and rows.size(1) % 4 == 0 and rows.data_ptr() % 8 == 0
+             and (bias is None or (bias.is_contiguous() and bias.data_ptr() % 8 == 0)),
+             'rows [P, d % 4 == 0], pos [T, k] contiguous, 8-byte aligned')
+    dev = _same_device(rows, pos)
+    T, k = pos.shape
+    d = rows.size(1)
+    lib = load_library()
+    with _on(dev):
+        out = torch.empty([T, d], dtype=torch.bfloat16, device=dev)
+        if T > 0:
+            rc = lib.spt_rows_combine_bf16(rows.data_ptr(), pos.data_ptr(), _ptr(bias), out.data_ptr(), T, k, d,
+                                           _stream(dev))
+            if rc != 0:
+                _raise(lib, rc, 'rows_combine_bf16')
+    return out

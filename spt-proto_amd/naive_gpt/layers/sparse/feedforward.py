@@ -9,6 +9,12 @@ the router probability (the LoRA variants in ``tuning/lora_ffn.py`` do).
 Evaluation goes through ``routing.routed_apply``: tokens are bucketed per block
 (every token appears in exactly k buckets) and each bucket runs a dense block
 GEMM; see that module for the MI355X mapping.
+
+bf16 layers (activations and every base weight bf16) take the grouped path on the bf16 kernels.
+The router's Linear stays a torch bf16 op; its probabilities are widened to fp32 for the bucketing
+(spt_route_topk), which ranks larger first and breaks exact ties towards the LOWER block index --
+torch.topk leaves the order of ties unspecified, and bf16 probabilities tie far more often than
+fp32 ones, so the loop and the grouped path may pick different blocks for a tied token.
 """
 import torch
 from torch import nn
@@ -23,13 +29,34 @@ def _make_router(d_model: int, n_blocks: int):
 
 def _grouped_usable(x: torch.Tensor, *frozen) -> bool:
     from . import grouped
+    if x.dtype == torch.bfloat16:
+        return grouped.bf16_usable(x, *frozen)
     return grouped.usable(x, *frozen)
+
+
+def _bf16_shapes_ok(x: torch.Tensor, d: int, bs: int) -> bool:
+    from . import grouped
+    return x.dtype != torch.bfloat16 or grouped.bf16_shapes(d, bs)
+
+
+def _loop_why(x: torch.Tensor, trainable: bool, d: int, bs: int, *weights):
+    """the fallback reason of the loop: a dtype mix, or bf16 shapes the bf16 kernels do not take, when
+    that is what sends the layer there"""
+    from . import grouped
+    mix = grouped.dtype_mix(x, *weights)
+    if mix:
+        return mix
+    if not _bf16_shapes_ok(x, d, bs):
+        return 'bf16 d_model {} / block {}: multiples of 64 only'.format(d, bs)
+    return 'x {} {}, trainable weights: {}'.format(tuple(x.shape), x.dtype, trainable)
 
 
 def _combine(ys: torch.Tensor, bk, x: torch.Tensor) -> torch.Tensor:
     """y[t] = sum of the token's rows of ys, in block order (the reference's `y[mask] += ...` loop
-    order): a fixed-order gather (spt_rows_combine) where that applies."""
+    order): a fixed-order gather (spt_rows_combine, spt_rows_combine_bf16) where that applies."""
     if ys.is_cuda and ys.dtype == torch.float32 and ys.size(1) % 4 == 0 and not ys.requires_grad:
+        return ext.rows_combine(ys.contiguous(), bk.pos)
+    if ys.is_cuda and ys.dtype == torch.bfloat16 and ys.size(1) % 4 == 0 and not ys.requires_grad:
         return ext.rows_combine(ys.contiguous(), bk.pos)
     return torch.zeros_like(x).index_add_(0, bk.token_long, ys)
 
@@ -64,7 +91,7 @@ class RoutedFFN(layers.Feedforward):
         from . import grouped
         nb, bs, d = self.n_blocks, self.block_size, self.d_model
         prob = self.router(x)
-        bk = grouped.make_buckets(prob.detach(), k=nb // 2)
+        bk = grouped.make_buckets(prob.detach().float(), k=nb // 2)      # (bf16: widened for the bucketing)
         h = grouped.grouped_linear(x, self.fc1.weight, bk.offsets, (bs, d, bs * d, d, 1),
                                    gather=bk.token, gather_long=bk.token_long,
                                    bias=self.fc1.bias.view([nb, bs]))
@@ -78,7 +105,11 @@ class RoutedFFN(layers.Feedforward):
         (grouped.RoutedFFNTrain).  The router only picks the blocks: no gradient reaches it."""
         from . import grouped
         prob = self.router(x)
-        bk = grouped.make_buckets(prob.detach(), k=self.n_blocks // 2)
+        bk = grouped.make_buckets(prob.detach().float(), k=self.n_blocks // 2)
+        if x.dtype == torch.bfloat16:
+            return grouped.RoutedFFNTrainBf16.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight,
+                                                    self.fc2.bias, bk.token, bk.offsets, bk.pos, self.n_blocks,
+                                                    grouped.activation_code(self.activation))
         return grouped.RoutedFFNTrain.apply(x, self.fc1.weight, self.fc1.bias, self.fc2.weight,
                                             self.fc2.bias, bk.token, bk.offsets, bk.pos, self.n_blocks,
                                             grouped.activation_code(self.activation))
@@ -89,26 +120,30 @@ class RoutedFFN(layers.Feedforward):
             return None, False
         if self.d_model % 4 != 0 or self.block_size % 4 != 0:
             return 'd_model {} / block {}: multiples of 4 only'.format(self.d_model, self.block_size), True
+        if not _bf16_shapes_ok(x, self.d_model, self.block_size):
+            return 'bf16 d_model {} / block {}: multiples of 64 only'.format(self.d_model, self.block_size), True
         return grouped.trainable_unusable(x, grouped.activation_code(self.activation), self.fc1.weight,
                                           self.fc1.bias, self.fc2.weight, self.fc2.bias), True
 
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         x = x.view([-1, self.d_model])
+        bf16 = x.dtype == torch.bfloat16
         if _grouped_usable(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias) \
-                and self.d_model % 4 == 0 and self.block_size % 4 == 0:
-            ext.note_path('routed_ffn_plain', 'grouped')
+                and self.d_model % 4 == 0 and self.block_size % 4 == 0 \
+                and _bf16_shapes_ok(x, self.d_model, self.block_size):
+            ext.note_path('routed_ffn_plain', 'grouped_bf16' if bf16 else 'grouped')
             return self._forward_grouped(x.contiguous()).view(x_size)
         why, on = self._trainable_unusable(x)
         if on and why is None:
-            ext.note_path('routed_ffn_plain', 'grouped_trainable')
+            ext.note_path('routed_ffn_plain', 'grouped_trainable_bf16' if bf16 else 'grouped_trainable')
             return self._forward_trainable(x.contiguous()).view(x_size)
         if on:
             ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda, why=lambda: why)
         else:
             ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
-                          why=lambda: 'x {} {}, trainable weights: {}'.format(
-                              tuple(x.shape), x.dtype, self.fc1.weight.requires_grad))
+                          why=lambda: _loop_why(x, self.fc1.weight.requires_grad, self.d_model, self.block_size,
+                                                self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 2)
         w1 = self.fc1.weight.view([self.n_blocks, self.block_size, -1])
@@ -149,7 +184,7 @@ class RoutedLLaMaFFN(layers.LLaMaFeedforward):
         from . import grouped
         nb, bs, d = self.n_blocks, self.block_size, self.d_model
         prob = self.router(x)
-        bk = grouped.make_buckets(prob.detach(), k=nb // 4)
+        bk = grouped.make_buckets(prob.detach().float(), k=nb // 4)
 
         def up(linear):
             return grouped.grouped_linear(x, linear.weight, bk.offsets, (bs, d, bs * d, d, 1),
@@ -163,7 +198,11 @@ class RoutedLLaMaFFN(layers.LLaMaFeedforward):
         """see RoutedFFN._forward_trainable (grouped.RoutedLLaMAFFNTrain)"""
         from . import grouped
         prob = self.router(x)
-        bk = grouped.make_buckets(prob.detach(), k=self.n_blocks // 4)
+        bk = grouped.make_buckets(prob.detach().float(), k=self.n_blocks // 4)
+        if x.dtype == torch.bfloat16:
+            return grouped.RoutedLLaMAFFNTrainBf16.apply(x, self.gate.weight, self.side.weight, self.down.weight,
+                                                         bk.token, bk.offsets, bk.pos, self.n_blocks,
+                                                         self.activation)
         return grouped.RoutedLLaMAFFNTrain.apply(x, self.gate.weight, self.side.weight, self.down.weight,
                                                  bk.token, bk.offsets, bk.pos, self.n_blocks, self.activation)
 
@@ -174,26 +213,30 @@ class RoutedLLaMaFFN(layers.LLaMaFeedforward):
         if self.n_blocks < 4 or self.d_model % 4 != 0 or self.block_size % 4 != 0:
             return 'n_blocks {}, d_model {} / block {}: >= 4 blocks, multiples of 4 only'.format(
                 self.n_blocks, self.d_model, self.block_size), True
+        if not _bf16_shapes_ok(x, self.d_model, self.block_size):
+            return 'bf16 d_model {} / block {}: multiples of 64 only'.format(self.d_model, self.block_size), True
         # (any activation: the gating product and its derivative are elementwise)
         return grouped.trainable_unusable(x, 0, self.gate.weight, self.side.weight, self.down.weight), True
 
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         x = x.view([-1, self.d_model])
+        bf16 = x.dtype == torch.bfloat16
         if self.n_blocks >= 4 and _grouped_usable(x, self.gate.weight, self.side.weight, self.down.weight) \
-                and self.d_model % 4 == 0 and self.block_size % 4 == 0:
-            ext.note_path('routed_ffn_plain', 'grouped')
+                and self.d_model % 4 == 0 and self.block_size % 4 == 0 \
+                and _bf16_shapes_ok(x, self.d_model, self.block_size):
+            ext.note_path('routed_ffn_plain', 'grouped_bf16' if bf16 else 'grouped')
             return self._forward_grouped(x.contiguous()).view(x_size)
         why, on = self._trainable_unusable(x)
         if on and why is None:
-            ext.note_path('routed_ffn_plain', 'grouped_trainable')
+            ext.note_path('routed_ffn_plain', 'grouped_trainable_bf16' if bf16 else 'grouped_trainable')
             return self._forward_trainable(x.contiguous()).view(x_size)
         if on:
             ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda, why=lambda: why)
         else:
             ext.note_path('routed_ffn_plain', 'torch_loop', fallback=x.is_cuda,
-                          why=lambda: 'x {} {}, trainable weights: {}'.format(
-                              tuple(x.shape), x.dtype, self.gate.weight.requires_grad))
+                          why=lambda: _loop_why(x, self.gate.weight.requires_grad, self.d_model, self.block_size,
+                                                self.gate.weight, self.side.weight, self.down.weight))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 4)
         gate = self.gate.weight.view([self.n_blocks, self.block_size, -1])

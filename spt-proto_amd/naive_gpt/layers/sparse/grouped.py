@@ -14,6 +14,11 @@ Row space: P = T * k rows, row p = the p-th (token, block) pair in block-major o
 Trainable base weights (the plain RoutedFFN / RoutedLLaMaFFN in training) take the grouped path
 too when ``TRAINABLE_WEIGHTS`` is on: their gradients are grouped products contracted over the
 bucket rows (``spt_grouped_gemm_wgrad``), written straight into the parameters' layouts.
+
+bf16 storage (the plain routed FFNs whose activations and weights are ALL bf16): the same bucketing
+(the router's probabilities widened to fp32 for it) and the bf16 kernels -- ``spt_grouped_gemm_bf16``,
+``spt_grouped_gemm_wgrad_bf16``, ``spt_rows_combine_bf16``, ``spt_swiglu_*_bf16``: fp32 accumulation of
+the exact products of the stored bf16 values, each result rounded once when stored.
 """
 import os
 from typing import NamedTuple
@@ -177,8 +182,32 @@ def grouped_linear(a, weight, offsets, view, gather=None, gather_long=None, bias
     return GroupedLinear.apply(a, weight, offsets, view, gather, gather_long, bias, rowscale)
 
 
+def dtype_mix(x: torch.Tensor, *weights):
+    """None when x and every given weight are all fp32 or all bf16, else what mixes (the grouped
+    paths take one storage type per layer: no silent conversion)."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        return 'x {}: fp32 or bf16 only'.format(x.dtype)
+    for w in weights:
+        if w is not None and w.dtype != x.dtype:
+            return 'x {} with a {} weight {}: one dtype per layer'.format(x.dtype, w.dtype, tuple(w.shape))
+    return None
+
+
+def bf16_shapes(d: int, bs: int) -> bool:
+    """spt_grouped_gemm_bf16 takes the routed FFN's four products (both views of fc1 / fc2 and their
+    swapped dX views) when d and the block size are multiples of 64 (k % 64, 16-byte rows)."""
+    return d % 64 == 0 and bs % 64 == 0
+
+
 def trainable_unusable(x: torch.Tensor, act, *weights):
     """None when the trainable grouped path takes these operands, else the reason it does not."""
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        if act is None:
+            return 'activation without a fused epilogue (ReLU, exact GELU, SiLU)'
+        for w in weights:
+            if not w.is_cuda or w.dtype != torch.bfloat16 or not w.is_contiguous():
+                return 'bf16 x with weight {} {}: bf16 contiguous CUDA weights only'.format(tuple(w.shape), w.dtype)
+        return None
     if not x.is_cuda or x.dtype != torch.float32:
         return 'x {} {} (fp32 CUDA activations only)'.format(tuple(x.shape), x.dtype)
     if act is None:
@@ -343,6 +372,138 @@ def usable(x: torch.Tensor, *frozen_weights) -> bool:
         if w.requires_grad or not w.is_contiguous() or w.dtype != torch.float32:
             return False
     return True
+
+
+def bf16_usable(x: torch.Tensor, *frozen_weights) -> bool:
+    """The bf16 grouped path of the PLAIN routed FFNs (feedforward.py; the LoRA routed variants keep
+    the fp32 gate above): bf16 CUDA activations and frozen bf16 base weights, every one of them."""
+    if not x.is_cuda or x.dtype != torch.bfloat16:
+        return False
+    for w in frozen_weights:
+        if w is None:
+            continue
+        if w.requires_grad or not w.is_contiguous() or w.dtype != torch.bfloat16:
+            return False
+    return True
+
+
+class RoutedFFNTrainBf16(torch.autograd.Function):
+    """RoutedFFNTrain on bf16 storage (x, weights, biases, activations and gradients bf16):
+
+        h  = act(x[token] W1_g^T + b1_g)      spt_grouped_gemm_bf16, EPI_ACT (pre-activation kept but for ReLU)
+        ys = h W2_g^T;  y = b2 + sum over the token's rows of ys     spt_grouped_gemm_bf16 + spt_rows_combine_bf16
+      backward
+        ds  = (dy[token] W2_g) * act'(s)      EPI_DACT
+        dW2 = dy[token]^T h,  dW1 = ds^T x[token] (+ db1) per block      spt_grouped_gemm_wgrad_bf16
+        dx  = sum over the token's rows of ds W1_g
+
+    The products of bf16 values are exact in the fp32 accumulator, so there is no near-the-kink
+    recomputation: the ReLU mask is the sign of the pre-activation the kernel computed (h > 0)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, token, offsets, pos, nb: int, act: int):
+        d_ff, d = w1.shape
+        bs, rows = d_ff // nb, token.numel()
+        relu = act == ext.ACT_RELU
+        h, s = ext.grouped_gemm_bf16(x, w1, offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1,
+                                     n_rows=rows, gather=token, bias=b1.detach().contiguous(),
+                                     epilogue=ext.EPI_ACT, activation=act, keep_preact=not relu)
+        ys = ext.grouped_gemm_bf16(h, w2, offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1,
+                                   n_rows=rows)
+        y = ext.rows_combine(ys, pos, bias=b2.detach().contiguous())
+        ctx.nb, ctx.act = nb, act
+        ctx.save_for_backward(x, h, s, w1, w2, token, offsets, pos)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, h, s, w1, w2, token, offsets, pos = ctx.saved_tensors
+        nb, act = ctx.nb, ctx.act
+        d_ff, d = w1.shape
+        bs, rows = d_ff // nb, token.numel()
+        dy = dy.contiguous()
+        ds = ext.grouped_gemm_bf16(dy, w2, offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff,
+                                   n_rows=rows, gather=token, epilogue=ext.EPI_DACT, activation=act,
+                                   h_in=h, s_in=s)
+        grad_w2 = grad_b2 = grad_w1 = grad_b1 = grad_x = None
+        if ctx.needs_input_grad[3]:
+            grad_w2 = ext.grouped_gemm_wgrad(dy, h, offsets, (d, bs, bs, d_ff, 1), rows,
+                                             gather_grad=token)[0].view(d, d_ff)
+        if ctx.needs_input_grad[4]:
+            grad_b2 = dy.sum(dim=0)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grad_w1, grad_b1 = ext.grouped_gemm_wgrad(ds, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                                      gather_a=token, want_bias=ctx.needs_input_grad[2])
+            grad_w1 = grad_w1.view(d_ff, d) if ctx.needs_input_grad[1] else None
+            grad_b1 = grad_b1.view(d_ff) if grad_b1 is not None else None
+        if ctx.needs_input_grad[0]:
+            dxs = ext.grouped_gemm_bf16(ds, w1, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
+                                        n_rows=rows)
+            grad_x = ext.rows_combine(dxs, pos)
+        return grad_x, grad_w1, grad_b1, grad_w2, grad_b2, None, None, None, None, None
+
+
+class RoutedLLaMAFFNTrainBf16(torch.autograd.Function):
+    """RoutedLLaMAFFNTrain on bf16 storage: the four grouped products on spt_grouped_gemm_bf16, the
+    gradients on spt_grouped_gemm_wgrad_bf16, h = silu(g) * sd and its derivative on
+    spt_swiglu_*_bf16 (another activation: torch, as on the fp32 path)."""
+
+    @staticmethod
+    def forward(ctx, x, wg, ws, wd, token, offsets, pos, nb: int, activation):
+        d_ff, d = wg.shape
+        bs, rows = d_ff // nb, token.numel()
+
+        def up(w):
+            return ext.grouped_gemm_bf16(x, w, offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1,
+                                         n_rows=rows, gather=token)
+
+        g, sd = up(wg), up(ws)
+        silu = isinstance(activation, torch.nn.SiLU) and ext.swiglu_bf16_supported(g, sd)
+        ext.note_path('swiglu', 'kernel_bf16' if silu else 'torch', fallback=not silu,
+                      why=lambda: 'activation {} on {}'.format(type(activation).__name__, tuple(g.shape)))
+        h = ext.swiglu_forward_bf16(g, sd) if silu else activation(g) * sd
+        ys = ext.grouped_gemm_bf16(h, wd, offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1,
+                                   n_rows=rows)
+        y = ext.rows_combine(ys, pos)
+        ctx.nb, ctx.activation, ctx.silu = nb, activation, silu
+        ctx.save_for_backward(x, g, sd, h, wg, ws, wd, token, offsets, pos)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, sd, h, wg, ws, wd, token, offsets, pos = ctx.saved_tensors
+        nb = ctx.nb
+        d_ff, d = wg.shape
+        bs, rows = d_ff // nb, token.numel()
+        dy = dy.contiguous()
+        dh = ext.grouped_gemm_bf16(dy, wd, offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff,
+                                   n_rows=rows, gather=token)
+        grad_wg = grad_ws = grad_wd = grad_x = None
+        if ctx.needs_input_grad[3]:
+            grad_wd = ext.grouped_gemm_wgrad(dy, h, offsets, (d, bs, bs, d_ff, 1), rows,
+                                             gather_grad=token)[0].view(d, d_ff)
+        if ctx.silu:
+            dg, dsd = ext.swiglu_backward_bf16(dh, g, sd)
+        else:
+            with torch.enable_grad():
+                g_ = g.detach().requires_grad_(True)
+                ag = ctx.activation(g_)
+                dg, = torch.autograd.grad(ag, g_, dh * sd)
+            dsd = dh * ag.detach()
+        del dh
+        if ctx.needs_input_grad[1]:
+            grad_wg = ext.grouped_gemm_wgrad(dg, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                             gather_a=token)[0].view(d_ff, d)
+        if ctx.needs_input_grad[2]:
+            grad_ws = ext.grouped_gemm_wgrad(dsd, x, offsets, (bs, d, bs * d, d, 1), rows,
+                                             gather_a=token)[0].view(d_ff, d)
+        if ctx.needs_input_grad[0]:
+            dxs = ext.grouped_gemm_bf16(dg, wg, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
+                                        n_rows=rows)
+            ext.grouped_gemm_bf16(dsd, ws, offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
+                                  n_rows=rows, out=dxs, accumulate=True)
+            grad_x = ext.rows_combine(dxs, pos)
+        return grad_x, grad_wg, grad_ws, grad_wd, None, None, None, None, None
 
 
 # ---------------------------------------------------------------- the fused LoRA routed FFN

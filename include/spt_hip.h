@@ -592,6 +592,26 @@ typedef struct SptGroupedGemmBf16 {
     int32_t pdot_ld;
 } SptGroupedGemmBf16;
 int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *desc, void *stream);
+/*
+ * spt_grouped_gemm_bf16 with the K extension of spt_grouped_gemm_fused (additive under ABI 40): the LoRA
+ * side product of the routed LoRA FFN on bf16 storage, added after rowscale and bias:
+ *     v[p, n] += sum_{j < r} a2[src2(p), j] * b2[g * b2_group_stride + n * b2_ldn + j]
+ * a2 fp32 [*, lda2] (src2 = gather2 ? gather2[p] : p), b2 bf16; b2_group_stride 0 = one table for every
+ * group.  a2 is split hi + lo (RNE bf16 parts) and each part multiplied exactly by b2: <= 2^-16 relative
+ * per product, fp32 accumulation.  Every epilogue of spt_grouped_gemm_bf16 and `accumulate`; both weight
+ * orientations (b2 stays k-contiguous).  Requires r % 4 == 0 and r <= 32 (SPT_EUNSUP), lda2 % 4 == 0,
+ * b2_ldn % 4 == 0, b2_group_stride % 4 == 0, a2 16-byte and b2 8-byte aligned (SPT_ESHAPE); the main
+ * operands as spt_grouped_gemm_bf16.
+ */
+typedef struct SptGroupedGemmBf16Ext {
+    const float *a2;           /* fp32 [*, lda2] */
+    const int32_t *gather2;    /* [n_rows] or NULL */
+    const void *b2;            /* bf16 */
+    int32_t lda2, r;
+    int64_t b2_group_stride;
+    int32_t b2_ldn;
+} SptGroupedGemmBf16Ext;
+int spt_grouped_gemm_bf16_ext(const SptGroupedGemmBf16 *desc, const SptGroupedGemmBf16Ext *ext, void *stream);
 /* spt_grouped_gemm_wgrad on bf16 G, A, out and dbias: same arguments, rules, chunking and in-order
  * reduction (fp32 chunk partials; bitwise reproducible, no atomics, capturable); out and dbias rounded
  * once.  Alignment: G, A, out and dbias 8-byte aligned (four bf16 per access), workspace 16-byte.  Products are exact without a rowscale; with one, rowscale * G is formed in fp32 and split
@@ -666,6 +686,21 @@ int spt_lora_down_grouped(const float *x, long long ldx, long long rows, int k, 
                           float *u, long long ldu, void *image, float *norms, void *stream);
 
 /*
+ * The down product on bf16 storage (the routed LoRA FFN in bf16): u[rows, n] = x[rows, k] . l[k, n] with x
+ * and l bf16 and u FP32 -- the products of bf16 values are exact, accumulated in fp32 in a fixed order
+ * (no `exact` switch, no image, no norms).  x row stride ldx elements; l contiguous; u row stride ldu
+ * (0 = n); u_block_major as spt_lora_down.  spt_lora_down_grouped_bf16: rows offsets[g] .. offsets[g + 1]
+ * - 1 use the table l + g * l_group_stride (n_groups <= 64, u_block_major not taken).  n % 4 == 0 and
+ * n <= 64 (u_block_major: n % 16 == 0), SPT_EUNSUP otherwise; k % 64 == 0, ldx % 8 == 0, x 16-byte and
+ * l 8-byte aligned, l_group_stride % 4 == 0 (SPT_ESHAPE).
+ */
+int spt_lora_down_bf16(const void *x, long long ldx, long long rows, int k, const void *l, int n,
+                       float *u, long long ldu, int u_block_major, void *stream);
+int spt_lora_down_grouped_bf16(const void *x, long long ldx, long long rows, int k, const void *l,
+                               long long l_group_stride, int n, const int32_t *offsets, int n_groups,
+                               float *u, long long ldu, void *stream);
+
+/*
  * Softmax cross-entropy of the language-model head (script/4-sparse-tuning-0.py:45-59:
  * nn.CrossEntropyLoss() on logits [rows, n_classes]), loss and gradient in one pass, IN PLACE:
  *   loss[i]      = log(sum_j exp(z[i, j])) - z[i, target[i]]           (0 for an ignored row)
@@ -726,6 +761,14 @@ int spt_tall_tn_batch(int count, const float *const *wides, long long ldw, const
                       long long ldn, const int32_t *gather, const int32_t *offsets, int n_groups,
                       long long rows, int width, int n, float *const *outs, int transposed,
                       void *workspace, void *stream);
+/* spt_tall_tn with a bf16 `wide` (widened on load) and a bf16 `out` [n_groups][width][n] (layout 0), each
+ * element rounded once (RNE) after the same in-order reduction of fp32 chunk sums: bitwise reproducible.
+ * narrow stays fp32 (ldn % 4 == 0, 16-byte aligned); wide 4-byte aligned, width and ldw even; n % 4 == 0,
+ * n <= 48 (SPT_EUNSUP).  gather / offsets as spt_tall_tn.  workspace: spt_tall_tn_bf16_workspace_bytes. */
+long long spt_tall_tn_bf16_workspace_bytes(long long rows, int n_groups, int width, int n);
+int spt_tall_tn_bf16(const void *wide, long long ldw, const float *narrow, long long ldn,
+                     const int32_t *gather, const int32_t *offsets, int n_groups, long long rows,
+                     int width, int n, void *out, void *workspace, void *stream);
 
 /*
  * Bucketing for the routed FFN: the k largest of the n_blocks router probabilities of every
@@ -812,6 +855,11 @@ int spt_swiglu_backward(const float *grad_h, const float *gate, const float *sid
 int spt_swiglu_forward_bf16(const void *gate, const void *side, void *h, long long n_elements, void *stream);
 int spt_swiglu_backward_bf16(const void *grad_h, const void *gate, const void *side, void *grad_gate,
                              void *grad_side, long long n_elements, void *stream);
+/* spt_swiglu_backward_bf16 on rows [rows, n] (n % 4 == 0) with the row dots of spt_swiglu_backward: dots
+ * [3, rows] fp32 = <grad_h, h>, <grad_gate, gate>, <grad_side, side> formed on the STORED bf16 values (h =
+ * bf16(silu(gate) * side), the rounded gradients); bf16 pointers 8-byte aligned, dots 4-byte. */
+int spt_swiglu_backward_dots_bf16(const void *grad_h, const void *gate, const void *side, void *grad_gate,
+                                  void *grad_side, float *dots, long long rows, int n, void *stream);
 
 /*
  * Gradient of table[ids] (the `left` table of a LoRA embedding, lora.py:118-126; autograd of

@@ -607,12 +607,12 @@ __device__ __forceinline__ void gi_mma(const GiFrags<NI> &f, f32x16 (&acc)[NI][2
         }
     }
 }
-template <int NI, int NA, bool KC_B>
+template <int NI, int NA, bool KC_B, bool BF16 = false>
 __device__ __forceinline__ void gi_contract(const GiLane<NI, NA> &c, const char *As, const char *Bs,
                                             int q2, f32x16 (&acc)[NI][2]) {
     GiFrags<NI> f;
     gi_read<NI, NA, KC_B>(c, As, Bs, q2, f);
-    gi_mma<NI>(f, acc);
+    gi_mma<NI, BF16>(f, acc);
 }
 // k-step k0 .. k0 + 31 into the LDS stage at `dma` (instruction t = wave + 4 j: 1 KiB each)
 // (BF16: k-steps of 64 bf16 -- the same 128 bytes per row of a KC tile, k0 * 2 bytes into the row)
@@ -692,7 +692,7 @@ __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restric
 template <int BM, bool BN_LAYOUT, int EPI, bool EXT, bool A32, bool BF16 = false>
 __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem, int bucket,
                                               int row_lo, int row_hi, int col_tile) {
-    static_assert(!(BF16 && (EXT || A32)), "bf16: no K extension, no fp32 rows");
+    static_assert(!(BF16 && A32), "bf16: no fp32 rows");
     constexpr int NI = BM / 64;                 // 32-row sub-blocks per wave
     constexpr int NA = BM / 32;                 // LDS-DMA instructions per wave: A tile
     constexpr int KS = BF16 ? 2 * GG_BK : GG_BK;    // k per stage
@@ -807,8 +807,47 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
     gg_scale_rows<NI>(g, acc, extras, wm);
 
     // ---- K extension: fp32 a2 [*, R] and b2 [n][R] split while staged into two KC tiles
-    // (R <= 32: one k-step, zero beyond R) ----
-    if (EXT) {
+    // (R <= 32: one k-step, zero beyond R).  BF16 (spt_grouped_gemm_bf16_ext): a2 is fp32 and b2 bf16;
+    // a2's hi goes to k 0 .. 31 of the stage, its lo to k 32 .. 63, b2's row to both halves, and the
+    // two plain products of a bf16 fragment pair form hi.b2 + lo.b2 (<= 2^-16 relative per product) ----
+    if (EXT && BF16) {
+        char *As = lds0, *Bs = lds0 + GI_TILE;
+        const int kq = tid & 7, k = 4 * kq;                 // 8 lanes per row: 4 k's each
+        auto put = [&](char *tile, int r, unsigned x0, unsigned x1, unsigned y0, unsigned y1) {
+            const int sw = (r >> 1) & 7;
+            char *row = tile + r * 128 + (kq & 1) * 8;
+            *reinterpret_cast<uint2 *>(row + (((kq >> 1) ^ sw) << 4)) = make_uint2(x0, x1);
+            *reinterpret_cast<uint2 *>(row + (((4 + (kq >> 1)) ^ sw) << 4)) = make_uint2(y0, y1);
+        };
+#pragma unroll
+        for (int u = 0; u < BM / 32; u++) {
+            const int r = (tid >> 3) + 32 * u;
+            const int p = row_lo + r;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p < row_hi && k < g.R) {
+                const long long src = g.gather2 ? g.gather2[p] : p;
+                v = *reinterpret_cast<const float4 *>(g.a2 + src * g.lda2 + k);
+            }
+            unsigned h0, l0, h1, l1;
+            gg_split2(v.x, v.y, h0, l0);
+            gg_split2(v.z, v.w, h1, l1);
+            put(As, r, h0, h1, l0, l1);
+        }
+        const unsigned short *b2 = reinterpret_cast<const unsigned short *>(g.b2);
+#pragma unroll
+        for (int u = 0; u < GG_BN / 32; u++) {
+            const int r = (tid >> 3) + 32 * u;
+            const int n = n0 + r;
+            uint2 b = make_uint2(0u, 0u);
+            if (n < g.N && k < g.R)
+                b = *reinterpret_cast<const uint2 *>(b2 + (size_t)bucket * g.b2_gstride + (size_t)n * g.b2_ldn + k);
+            put(Bs, r, b.x, b.y, b.x, b.y);
+        }
+        __syncthreads();
+        gi_contract<NI, NA, true, true>(c, As, Bs, 0, acc);
+        if (g.R > 16) gi_contract<NI, NA, true, true>(c, As, Bs, 1, acc);
+        __syncthreads();
+    } else if (EXT) {
         char *As = lds0, *Bs = lds0 + GI_TILE;
         const int kq = tid & 7, k = 4 * kq;                 // 8 lanes per row: 4 k's each
         auto put4 = [&](char *tile, int r, const float4 &v) {
@@ -1650,6 +1689,20 @@ __global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_bf16_kernel(Groupe
                                                                      w.col_tile);
 }
 
+// spt_grouped_gemm_bf16_ext: the same with the fp32-a2 / bf16-b2 K extension after the scaling
+template <bool BN_LAYOUT, int EPI>
+__global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_bf16_ext_kernel(GroupedArgs g) {
+    __shared__ __attribute__((aligned(1024))) float smem[GI_LDS_FLOATS + GG_EXTRAS];
+    const GgWork w = gg_find_work(g);
+    if (w.bucket < 0) return;
+    if (w.half < 0)
+        gemm_tile_img<GG_BM, BN_LAYOUT, EPI, true, false, true>(g, smem, w.bucket, w.row_lo, w.row_hi,
+                                                                w.col_tile);
+    else
+        gemm_tile_img<GG_BM / 2, BN_LAYOUT, EPI, true, false, true>(g, smem, w.bucket, w.row_lo, w.row_hi,
+                                                                    w.col_tile);
+}
+
 // fp32 [rows, cols] (leading dimension ld) -> the bf16 image [row][cols / 32][hi | lo][32]:
 // a thread converts 8 consecutive columns (32 bytes in, 16 + 16 bytes out); columns past
 // `cols` inside the last block are zero.
@@ -2360,7 +2413,8 @@ extern "C" int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const i
                         out, group_stride, ldn, dbias, workspace, stream);
 }
 
-extern "C" int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *d, void *stream) {
+// spt_grouped_gemm_bf16 and, with `x` != NULL, spt_grouped_gemm_bf16_ext
+static int launch_grouped_bf16(const SptGroupedGemmBf16 *d, const SptGroupedGemmBf16Ext *x, void *stream) {
     if (!d) return SPT_EINVAL;
     if (!d->a || !d->w || !d->offsets || !d->out) return SPT_EINVAL;
     if (d->n_rows <= 0 || d->k <= 0 || d->n <= 0 || d->n_groups <= 0 || d->lda < d->k) return SPT_EINVAL;
@@ -2403,10 +2457,36 @@ extern "C" int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *d, void *stream) 
     g.pdot_main = d->pdot_main; g.pdot_act = d->pdot_act; g.pdot_ld = d->pdot_ld;
     g.a_rowb = (long long)d->lda * 2;
     g.w_rowb = (long long)(d->w_ldk == 1 ? d->w_ldn : d->w_ldk) * 2;
+    if (x) {
+        // the K extension: fp32 a2 rows as float4 (16 bytes), bf16 b2 rows as four values (8 bytes)
+        if (!x->a2 || !x->b2 || x->r <= 0 || x->lda2 < x->r || x->b2_ldn < x->r || x->b2_group_stride < 0)
+            return SPT_EINVAL;
+        if (x->r % 4 != 0 || x->r > GG_BK) return SPT_EUNSUP;
+        if (x->lda2 % 4 != 0 || x->b2_ldn % 4 != 0 || x->b2_group_stride % 4 != 0 || misaligned(x->a2, 15) ||
+            misaligned(x->b2, 7))
+            return SPT_ESHAPE;
+        g.a2 = x->a2; g.gather2 = x->gather2; g.b2 = static_cast<const float *>(x->b2);
+        g.lda2 = x->lda2; g.R = x->r; g.b2_gstride = x->b2_group_stride; g.b2_ldn = x->b2_ldn;
+    }
     g.slots = resident_slots();
     if (g.slots <= 0) return SPT_EINVAL;
     const dim3 grid(2 * row_tiles * col_tiles);
     hipStream_t s = (hipStream_t)stream;
+    if (x) {
+#define SPT_GBX(BN)                                                                                            \
+    do {                                                                                                       \
+        if (epilogue == EPI_PLAIN)                                                                             \
+            hipLaunchKernelGGL((grouped_gemm_bf16_ext_kernel<BN, EPI_PLAIN>), grid, dim3(GG_THREADS), 0, s, g); \
+        else if (epilogue == EPI_ACT)                                                                          \
+            hipLaunchKernelGGL((grouped_gemm_bf16_ext_kernel<BN, EPI_ACT>), grid, dim3(GG_THREADS), 0, s, g);   \
+        else                                                                                                   \
+            hipLaunchKernelGGL((grouped_gemm_bf16_ext_kernel<BN, EPI_DACT>), grid, dim3(GG_THREADS), 0, s, g);  \
+    } while (0)
+        if (d->w_ldk == 1) SPT_GBX(false); else SPT_GBX(true);
+#undef SPT_GBX
+        SPT_LAUNCH_CHECK();
+        return SPT_OK;
+    }
 #define SPT_GB(BN)                                                                                         \
     do {                                                                                                   \
         if (epilogue == EPI_PLAIN)                                                                         \
@@ -2420,6 +2500,16 @@ extern "C" int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *d, void *stream) 
 #undef SPT_GB
     SPT_LAUNCH_CHECK();
     return SPT_OK;
+}
+
+extern "C" int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *d, void *stream) {
+    return launch_grouped_bf16(d, nullptr, stream);
+}
+
+extern "C" int spt_grouped_gemm_bf16_ext(const SptGroupedGemmBf16 *d, const SptGroupedGemmBf16Ext *ext,
+                                         void *stream) {
+    if (!ext) return SPT_EINVAL;
+    return launch_grouped_bf16(d, ext, stream);
 }
 
 extern "C" int spt_rows_combine_bf16(const void *rows, const int32_t *pos, const void *bias, void *out,

@@ -40,6 +40,12 @@ namespace spt {
 typedef __attribute__((ext_vector_type(8))) __bf16 ls_bf16x8;
 typedef __attribute__((ext_vector_type(2))) __bf16 ls_bf16x2;
 typedef __attribute__((ext_vector_type(2))) float ls_f32x2;
+__device__ __forceinline__ unsigned short ls_bf_round(float a) {       // RNE
+    const ls_f32x2 x = {a, 0.0f};
+    return (unsigned short)__builtin_bit_cast(unsigned, __builtin_convertvector(x, ls_bf16x2));
+}
+typedef __attribute__((ext_vector_type(2))) __bf16 ls_bf16x2;
+typedef __attribute__((ext_vector_type(2))) float ls_f32x2;
 typedef __attribute__((ext_vector_type(4))) float ls_f32x4;
 
 // two floats -> packed bf16 pairs (first value in the low half): hi = RNE, lo = RNE(x - hi)
@@ -396,11 +402,13 @@ struct TnBatch {
     float *out[TN_BATCH];
 };
 
-template <int N, int UNROLL, bool GATHER>
-__global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_kernel(
+// BF16 (spt_tall_tn_bf16): `wide` holds bf16, widened on load (two columns = 4 bytes per lane); `narrow`
+// has n <= N columns (the rest of the chunk's N are zero)
+template <int N, int UNROLL, bool GATHER, bool BF16>
+__device__ __forceinline__ void tall_tn_partial(
     TnBatch batch, long long ldw, long long ldn,
     const int32_t *__restrict__ gather, const int32_t *__restrict__ offsets, int G, long long R, int W,
-    float *__restrict__ partial) {
+    float *__restrict__ partial, int n) {
     constexpr int JB = N < 16 ? N : 16;                      // table columns per reduction pass
     __shared__ float2 red[TN_WAVES][JB][64];
     const float *__restrict__ wide = batch.wide[blockIdx.z];
@@ -424,10 +432,17 @@ __global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_kernel(
     // workgroup of the launch is resident at once, so nothing else hides its prologue
     float2 vn[UNROLL];
     const float *wp = wide + (row0 + wr0) * ldw + col;
+    const unsigned short *wpb = reinterpret_cast<const unsigned short *>(wide) + (row0 + wr0) * ldw + col;
     auto request = [&](int r0) {
 #pragma unroll
-        for (int u = 0; u < UNROLL; u++)                     // rows past the end: clamped, weight 0
-            vn[u] = *reinterpret_cast<const float2 *>(wp + (long long)min(r0 + u, wrows - 1) * ldw);
+        for (int u = 0; u < UNROLL; u++) {                   // rows past the end: clamped, weight 0
+            if constexpr (BF16) {
+                const unsigned v = *reinterpret_cast<const unsigned *>(wpb + (long long)min(r0 + u, wrows - 1) * ldw);
+                vn[u] = make_float2(__builtin_bit_cast(float, v << 16), __builtin_bit_cast(float, v & 0xffff0000u));
+            } else {
+                vn[u] = *reinterpret_cast<const float2 *>(wp + (long long)min(r0 + u, wrows - 1) * ldw);
+            }
+        }
     };
     if (wrows > 0) request(0);
     // the chunk's rows of `narrow` -> LDS (the memory of `red`, free until the sums are formed):
@@ -438,7 +453,10 @@ __global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_kernel(
     for (int i = threadIdx.x; i < rows * (N / 4); i += 64 * TN_WAVES) {
         const int r = i / (N / 4), q = i - r * (N / 4);
         const long long src = GATHER ? (long long)gather[row0 + r] : row0 + r;
-        reinterpret_cast<float4 *>(nar)[i] = *reinterpret_cast<const float4 *>(narrow + src * ldn + 4 * q);
+        if (BF16 && 4 * q >= n)
+            reinterpret_cast<float4 *>(nar)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else
+            reinterpret_cast<float4 *>(nar)[i] = *reinterpret_cast<const float4 *>(narrow + src * ldn + 4 * q);
     }
     __syncthreads();
     if (wrows > 0) {
@@ -486,12 +504,31 @@ __global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_kernel(
     }
 }
 
+template <int N, int UNROLL, bool GATHER>
+__global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_kernel(
+    TnBatch batch, long long ldw, long long ldn,
+    const int32_t *__restrict__ gather, const int32_t *__restrict__ offsets, int G, long long R, int W,
+    float *__restrict__ partial) {
+    tall_tn_partial<N, UNROLL, GATHER, false>(batch, ldw, ldn, gather, offsets, G, R, W, partial, N);
+}
+
+template <int N, int UNROLL, bool GATHER>
+__global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_bf16_kernel(
+    TnBatch batch, long long ldw, long long ldn,
+    const int32_t *__restrict__ gather, const int32_t *__restrict__ offsets, int G, long long R, int W,
+    float *__restrict__ partial, int n) {
+    tall_tn_partial<N, UNROLL, GATHER, true>(batch, ldw, ldn, gather, offsets, G, R, W, partial, n);
+}
+
 // out[g][w][j] (or transposed: out[g][j][w]) = sum over the chunks of group g.  A workgroup = 64
 // elements x 4 slices of the chunk range (consecutive quarters), the slices added in order: fixed
 // summation tree.  (One thread per element: 16 K threads on 64 CUs, 8 us for 4 MB.)
-__global__ __launch_bounds__(256) void tall_tn_reduce_kernel(
+// (BF16: out holds bf16, each element rounded once; `n` is the chunks' padded column count, nout <= n
+// the table's, layout 0 only)
+template <bool BF16>
+__device__ __forceinline__ void tall_tn_reduce(
     const float *__restrict__ partial, const int32_t *__restrict__ offsets, int G, int W, int n,
-    int nchunks, TnBatch batch, int transposed) {
+    int nchunks, TnBatch batch, int transposed, int nout) {
     __shared__ float slice_sum[4][64];
     float *__restrict__ out = batch.out[blockIdx.z];
     partial += (size_t)blockIdx.z * nchunks * n * W;
@@ -527,11 +564,29 @@ __global__ __launch_bounds__(256) void tall_tn_reduce_kernel(
         const float v = (slice_sum[0][lane] + slice_sum[1][lane]) + (slice_sum[2][lane] + slice_sum[3][lane]);
         const int j = e / W, w = e - j * W;
         // layout 0: [w][j]; 1: [j][w]; 2: [j / 16][w][16] (rank-16 tables side by side: each its own matrix)
-        const size_t at = transposed == 1 ? (size_t)e
-                        : transposed == 2 ? ((size_t)(j >> 4) * W + w) * 16 + (j & 15)
-                                          : (size_t)w * n + j;
-        out[(size_t)g * W * n + at] = v;
+        if constexpr (BF16) {
+            if (j < nout) {
+                reinterpret_cast<unsigned short *>(out)[((size_t)g * W + w) * nout + j] = ls_bf_round(v);
+            }
+        } else {
+            const size_t at = transposed == 1 ? (size_t)e
+                            : transposed == 2 ? ((size_t)(j >> 4) * W + w) * 16 + (j & 15)
+                                              : (size_t)w * n + j;
+            out[(size_t)g * W * n + at] = v;
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void tall_tn_reduce_kernel(
+    const float *__restrict__ partial, const int32_t *__restrict__ offsets, int G, int W, int n,
+    int nchunks, TnBatch batch, int transposed) {
+    tall_tn_reduce<false>(partial, offsets, G, W, n, nchunks, batch, transposed, n);
+}
+
+__global__ __launch_bounds__(256) void tall_tn_reduce_bf16_kernel(
+    const float *__restrict__ partial, const int32_t *__restrict__ offsets, int G, int W, int n,
+    int nchunks, TnBatch batch, int nout) {
+    tall_tn_reduce<true>(partial, offsets, G, W, n, nchunks, batch, 0, nout);
 }
 
 }  // namespace spt
@@ -600,4 +655,204 @@ extern "C" int spt_tall_tn_batch(int count, const float *const *wides, long long
                                  void *stream) {
     return tall_tn_any(count, wides, ldw, narrows, ldn, gather, offsets, n_groups, rows, width, n, outs,
                        transposed, workspace, stream);
+}
+
+extern "C" long long spt_tall_tn_bf16_workspace_bytes(long long rows, int n_groups, int width, int n) {
+    if (rows <= 0 || n_groups <= 0 || width <= 0 || n <= 0 || n > 48) return 0;
+    const int np = n <= 4 ? 4 : n <= 16 ? 16 : n <= 32 ? 32 : 48;        // the chunks' padded columns
+    return spt_tall_tn_workspace_bytes(rows, n_groups, width, np);
+}
+
+extern "C" int spt_tall_tn_bf16(const void *wide, long long ldw, const float *narrow, long long ldn,
+                                const int32_t *gather, const int32_t *offsets, int n_groups, long long rows,
+                                int width, int n, void *out, void *workspace, void *stream) {
+    if (!wide || !narrow || !out || !workspace) return SPT_EINVAL;
+    if (rows <= 0 || width <= 0 || n <= 0 || n_groups <= 0 || ldw < width || ldn < n) return SPT_EINVAL;
+    if (!offsets && n_groups != 1) return SPT_EINVAL;
+    if (n % 4 != 0 || n > 48) return SPT_EUNSUP;
+    if (n_groups > 64 || rows > 0x7FFFFFFFll) return SPT_EUNSUP;
+    if (width % 2 != 0 || ldw % 2 != 0 || ldn % 4 != 0) return SPT_ESHAPE;
+    if ((reinterpret_cast<uintptr_t>(wide) & 3) != 0 || !ls_aligned(narrow) ||
+        (reinterpret_cast<uintptr_t>(out) & 1) != 0)
+        return SPT_ESHAPE;
+    TnBatch batch = {};
+    batch.wide[0] = static_cast<const float *>(wide);
+    batch.narrow[0] = narrow;
+    batch.out[0] = static_cast<float *>(out);
+    const int np = n <= 4 ? 4 : n <= 16 ? 16 : n <= 32 ? 32 : 48;
+    const int nchunks = (int)((rows + TN_RC - 1) / TN_RC) + (offsets ? n_groups : 0);
+    hipStream_t s = (hipStream_t)stream;
+    float *partial = static_cast<float *>(workspace);
+    const dim3 grid(nchunks, (width + TN_COLS - 1) / TN_COLS, 1);
+#define SPT_TNB(N, U)                                                                                   \
+    do {                                                                                                \
+        if (gather)                                                                                     \
+            hipLaunchKernelGGL((tall_tn_partial_bf16_kernel<N, U, true>), grid, dim3(64 * TN_WAVES), 0, s, \
+                               batch, ldw, ldn, gather, offsets, n_groups, rows, width, partial, n);    \
+        else                                                                                            \
+            hipLaunchKernelGGL((tall_tn_partial_bf16_kernel<N, U, false>), grid, dim3(64 * TN_WAVES), 0, s, \
+                               batch, ldw, ldn, gather, offsets, n_groups, rows, width, partial, n);    \
+    } while (0)
+    if (np == 4) SPT_TNB(4, 8);
+    else if (np == 16) SPT_TNB(16, 8);
+    else if (np == 32) SPT_TNB(32, 4);
+    else SPT_TNB(48, 4);
+#undef SPT_TNB
+    SPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tall_tn_reduce_bf16_kernel, dim3((width * np + 63) / 64, n_groups, 1), dim3(256), 0, s,
+                       partial, offsets, n_groups, width, np, nchunks, batch, n);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+// ---- the down product on bf16 storage (spt_lora_down_bf16 / _grouped_bf16) ---------------------
+// u[rows, n] (fp32) = x[rows, k] (bf16) . l[k, n] (bf16): every product of two bf16 values is exact in
+// fp32, accumulated in fp32 -- no split, no `exact` switch, no image or norms (the bf16 GEMMs read the
+// bf16 activation as it is).  A workgroup owns 64 rows (a lane each, all n columns in registers); its four
+// waves take interleaved 64-k slices of the contraction (one 128-byte line of a row per slice), the
+// table's 256-k chunk sits in LDS as bf16 (read as wave-wide broadcasts), and the four waves' sums are
+// added in wave order through LDS: a fixed summation order, reproducible.
+namespace spt {
+
+constexpr int LB_ROWS = 64;         // rows per workgroup
+constexpr int LB_KS = 64;           // k per wave and slice
+constexpr int LB_KC = 4 * LB_KS;    // k per chunk (four waves)
+
+// workgroup b -> (group, first row, rows); groups' tiles are consecutive (grid: ceil(rows / 64) + G)
+__device__ __forceinline__ void lb_tile(const int32_t *offsets, int G, long long R, int b, int &g,
+                                        long long &row0, int &rows) {
+    if (!offsets) { g = 0; row0 = (long long)b * LB_ROWS; rows = (int)min((long long)LB_ROWS, R - row0); return; }
+    int base = 0;
+    g = -1; row0 = 0; rows = 0;
+    for (int i = 0; i < G; i++) {
+        const long long lo = offsets[i], hi = offsets[i + 1];
+        const int nt = (int)((hi - lo + LB_ROWS - 1) / LB_ROWS);
+        if (g < 0 && b < base + nt) {
+            g = i; row0 = lo + (long long)(b - base) * LB_ROWS;
+            rows = (int)min((long long)LB_ROWS, hi - row0);
+        }
+        base += nt;
+    }
+}
+
+template <int NP>
+__global__ __launch_bounds__(256) void lora_down_bf16_kernel(
+    const unsigned short *__restrict__ x, long long ldx, long long R, int K,
+    const unsigned short *__restrict__ l, long long l_gstride, int n,
+    const int32_t *__restrict__ offsets, int G, float *__restrict__ u, long long ldu, int block_major) {
+    // the table chunk [LB_KC][NP] bf16 (8 .. 32 KiB), later the waves' sums [4][16][64] fp32 (16 KiB)
+    constexpr int LDS_BYTES = LB_KC * NP * 2 > 4 * 16 * 64 * 4 ? LB_KC * NP * 2 : 4 * 16 * 64 * 4;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
+    auto tab = reinterpret_cast<unsigned short (*)[NP]>(lds);
+    int g, rows; long long row0;
+    lb_tile(offsets, G, R, blockIdx.x, g, row0, rows);
+    if (rows <= 0) return;                                   // (the whole workgroup)
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned short *tg = l + (size_t)g * l_gstride;
+    const unsigned short *xr = x + (row0 + min(lane, rows - 1)) * ldx;      // (clamped rows: not stored)
+    float acc[NP];
+#pragma unroll
+    for (int j = 0; j < NP; j++) acc[j] = 0.0f;
+    for (int k0 = 0; k0 < K; k0 += LB_KC) {
+        // the chunk's table rows -> LDS, four columns (8 bytes) per access, zero past k and n
+        for (int i = threadIdx.x; i < LB_KC * (NP / 4); i += 256) {
+            const int kr = i / (NP / 4), c = 4 * (i - kr * (NP / 4));
+            uint2 v = make_uint2(0u, 0u);
+            if (k0 + kr < K && c < n) v = *reinterpret_cast<const uint2 *>(tg + (size_t)(k0 + kr) * n + c);
+            *reinterpret_cast<uint2 *>(&tab[kr][c]) = v;
+        }
+        __syncthreads();
+        const int ks = k0 + wave * LB_KS;
+        if (ks < K) {
+            uint4 xv[LB_KS / 8];
+#pragma unroll
+            for (int q = 0; q < LB_KS / 8; q++) xv[q] = *reinterpret_cast<const uint4 *>(xr + ks + 8 * q);
+#pragma unroll
+            for (int q = 0; q < LB_KS / 8; q++) {
+                const unsigned w[4] = {xv[q].x, xv[q].y, xv[q].z, xv[q].w};
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const float a = __builtin_bit_cast(float, (e & 1) ? (w[e >> 1] & 0xffff0000u) : (w[e >> 1] << 16));
+                    const unsigned short *tr = &tab[wave * LB_KS + 8 * q + e][0];
+#pragma unroll
+                    for (int j8 = 0; j8 < NP / 8; j8++) {
+                        const uint4 t = *reinterpret_cast<const uint4 *>(tr + 8 * j8);   // broadcast
+                        const unsigned tw[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                        for (int jj = 0; jj < 8; jj++) {
+                            const float b = __builtin_bit_cast(float, (jj & 1) ? (tw[jj >> 1] & 0xffff0000u)
+                                                                               : (tw[jj >> 1] << 16));
+                            acc[8 * j8 + jj] = fmaf(a, b, acc[8 * j8 + jj]);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the four waves' sums in wave order, 16 columns at a time (the table's LDS is free now)
+    float *red = reinterpret_cast<float *>(lds);            // [4][16][64]
+#pragma unroll
+    for (int jb = 0; jb < NP; jb += 16) {
+#pragma unroll
+        for (int jj = 0; jj < 16; jj++) red[(wave * 16 + jj) * 64 + lane] = acc[jb + jj];
+        __syncthreads();
+        for (int o = threadIdx.x; o < 16 * 64; o += 256) {
+            const int jj = o >> 6, r = o & 63, j = jb + jj;
+            const float v = ((red[jj * 64 + r] + red[(16 + jj) * 64 + r]) + red[(32 + jj) * 64 + r]) +
+                            red[(48 + jj) * 64 + r];
+            if (r < rows && j < n) {
+                const long long p = row0 + r;
+                // block_major: n / 16 matrices [R, 16] one after the other
+                const size_t at = block_major ? ((size_t)(j >> 4) * R + p) * 16 + (j & 15) : (size_t)p * ldu + j;
+                u[at] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace spt
+
+static int lora_down_bf16_any(const void *x, long long ldx, long long rows, int k, const void *l,
+                              long long l_gstride, int n, const int32_t *offsets, int n_groups, float *u,
+                              long long ldu, int u_block_major, void *stream) {
+    if (!x || !l || !u) return SPT_EINVAL;
+    if (rows <= 0 || k <= 0 || n <= 0 || n_groups <= 0 || ldx < k || l_gstride < 0) return SPT_EINVAL;
+    if (ldu == 0) ldu = n;
+    if (ldu < n) return SPT_EINVAL;
+    if (n % 4 != 0 || n > 64 || (u_block_major && n % 16 != 0)) return SPT_EUNSUP;
+    if (n_groups > 64 || rows > 0x7FFFFFFFll) return SPT_EUNSUP;
+    if (offsets && u_block_major) return SPT_EUNSUP;
+    if (k % LB_KS != 0 || ldx % 8 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(l) & 7) != 0 || l_gstride % 4 != 0)
+        return SPT_ESHAPE;
+    const unsigned blocks = (unsigned)((rows + LB_ROWS - 1) / LB_ROWS + (offsets ? n_groups : 0));
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned short *xb = static_cast<const unsigned short *>(x), *lb = static_cast<const unsigned short *>(l);
+#define SPT_LB(NP)                                                                                        \
+    hipLaunchKernelGGL((lora_down_bf16_kernel<NP>), dim3(blocks), dim3(256), 0, s, xb, ldx, rows, k, lb,   \
+                       l_gstride, n, offsets, n_groups, u, ldu, u_block_major)
+    // (n below a multiple of 16: the table's columns past n are zero in LDS, u's are not stored)
+    if (n <= 16) SPT_LB(16);
+    else if (n <= 32) SPT_LB(32);
+    else if (n <= 48) SPT_LB(48);
+    else SPT_LB(64);
+#undef SPT_LB
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_lora_down_bf16(const void *x, long long ldx, long long rows, int k, const void *l, int n,
+                                  float *u, long long ldu, int u_block_major, void *stream) {
+    return lora_down_bf16_any(x, ldx, rows, k, l, 0, n, nullptr, 1, u, ldu, u_block_major, stream);
+}
+
+extern "C" int spt_lora_down_grouped_bf16(const void *x, long long ldx, long long rows, int k, const void *l,
+                                          long long l_group_stride, int n, const int32_t *offsets,
+                                          int n_groups, float *u, long long ldu, void *stream) {
+    if (!offsets) return SPT_EINVAL;
+    if (l_group_stride < (long long)k * n) return SPT_EINVAL;
+    return lora_down_bf16_any(x, ldx, rows, k, l, l_group_stride, n, offsets, n_groups, u, ldu, 0, stream);
 }

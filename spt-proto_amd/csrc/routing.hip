@@ -568,3 +568,65 @@ extern "C" int spt_ffn_coeff_grad(const float *dot_main, const float *dot_act, i
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }
+
+// spt_swiglu_backward_dots_bf16: spt_swiglu_backward_bf16 plus the three row dots of spt_swiglu_backward, a wave
+// per row.  The dots are formed on the STORED values -- <grad_h, bf16(h)>, <bf16(grad_gate), gate>,
+// <bf16(grad_side), side> -- the same values the rank-r products of the coefficient gradient see (h . Ld,
+// grad_gate . Rg, grad_side . Rs), so their LoRA parts cancel against those products.
+namespace spt {
+__device__ __forceinline__ float sw_round(float a) {
+    const sw_f32x2 x = {a, 0.0f};
+    return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, __builtin_convertvector(x, sw_bf16x2)) << 16);
+}
+
+__global__ __launch_bounds__(256) void swiglu_backward_dots_bf16_kernel(
+    const unsigned short *__restrict__ dh, const unsigned short *__restrict__ g,
+    const unsigned short *__restrict__ s, unsigned short *__restrict__ dg, unsigned short *__restrict__ ds,
+    float *__restrict__ dots, long long rows, int n) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                     // (a wave leaves as a whole)
+    const size_t base = (size_t)row * n;
+    float d_h = 0.0f, d_g = 0.0f, d_s = 0.0f;
+    for (int c = 4 * lane; c < n; c += 256) {
+        const float4 vdh = sw_load4(dh + base + c), vg = sw_load4(g + base + c), vs = sw_load4(s + base + c);
+        const float xdh[4] = {vdh.x, vdh.y, vdh.z, vdh.w}, xg[4] = {vg.x, vg.y, vg.z, vg.w},
+                    xs[4] = {vs.x, vs.y, vs.z, vs.w};
+        float og[4], os[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const float a = silu_f(xg[e]);
+            os[e] = sw_round(xdh[e] * a);
+            og[e] = sw_round(xdh[e] * xs[e] * silu_grad_f(xg[e]));
+            d_h = fmaf(xdh[e], sw_round(a * xs[e]), d_h);
+            d_g = fmaf(og[e], xg[e], d_g);
+            d_s = fmaf(os[e], xs[e], d_s);
+        }
+        sw_store4(dg + base + c, og[0], og[1], og[2], og[3]);
+        sw_store4(ds + base + c, os[0], os[1], os[2], os[3]);
+    }
+    d_h = group_sum<64>(d_h);
+    d_g = group_sum<64>(d_g);
+    d_s = group_sum<64>(d_s);
+    if (lane == 0) {
+        dots[row] = d_h;
+        dots[rows + row] = d_g;
+        dots[2 * rows + row] = d_s;
+    }
+}
+}  // namespace spt
+
+extern "C" int spt_swiglu_backward_dots_bf16(const void *grad_h, const void *gate, const void *side, void *grad_gate,
+                                             void *grad_side, float *dots, long long rows, int n, void *stream) {
+    if (!grad_h || !gate || !side || !grad_gate || !grad_side || !dots) return SPT_EINVAL;
+    if (rows <= 0 || n <= 0 || rows > 0x7FFFFFFFll * 4) return SPT_EINVAL;
+    if (!sw_bf16_args(n, {grad_h, gate, side, grad_gate, grad_side}) || (reinterpret_cast<uintptr_t>(dots) & 3) != 0)
+        return SPT_ESHAPE;
+    hipLaunchKernelGGL(swiglu_backward_dots_bf16_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, static_cast<const unsigned short *>(grad_h),
+                       static_cast<const unsigned short *>(gate), static_cast<const unsigned short *>(side),
+                       static_cast<unsigned short *>(grad_gate), static_cast<unsigned short *>(grad_side), dots,
+                       rows, n);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}

@@ -80,6 +80,15 @@ _PROTOTYPES = {
                                + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
                                   ctypes.c_longlong] + [_c_ptr] * 3, _c_int),
     'spt_grouped_gemm_bf16': ([_c_ptr, _c_ptr], _c_int),
+    'spt_grouped_gemm_bf16_ext': ([_c_ptr, _c_ptr, _c_ptr], _c_int),
+    'spt_lora_down_bf16': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int, _c_ptr,
+                            ctypes.c_longlong, _c_int, _c_ptr], _c_int),
+    'spt_lora_down_grouped_bf16': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, ctypes.c_longlong,
+                                    _c_int, _c_ptr, _c_int, _c_ptr, ctypes.c_longlong, _c_ptr], _c_int),
+    'spt_tall_tn_bf16_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
+    'spt_tall_tn_bf16': ([_c_ptr, ctypes.c_longlong, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, _c_int,
+                          ctypes.c_longlong, _c_int, _c_int, _c_ptr, _c_ptr, _c_ptr], _c_int),
+    'spt_swiglu_backward_dots_bf16': ([_c_ptr] * 6 + [ctypes.c_longlong, _c_int, _c_ptr], _c_int),
     'spt_grouped_gemm_wgrad_bf16_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
     'spt_grouped_gemm_wgrad_bf16': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, ctypes.c_longlong] + [_c_ptr] * 3
                                     + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
@@ -2156,3 +2165,202 @@ def _rows_combine_bf16(rows: torch.Tensor, pos: torch.Tensor, bias, side) -> tor
             if rc != 0:
                 _raise(lib, rc, 'rows_combine_bf16')
     return out
+
+
+# ---------------------------------------------------------------- the routed LoRA FFN on bf16 storage
+# (layers/sparse/grouped.py: RoutedLoRAFFNBf16 / RoutedLoRALLaMAFFNBf16).  The rank-r intermediates are
+# fp32 (u, z, dzt, du): the only fp32 operands these entries take are `a2` of the GEMM's K extension and
+# `narrow` of tall_tn_bf16; every other tensor is bf16.
+
+class _GroupedExtBf16(ctypes.Structure):
+    """``SptGroupedGemmBf16Ext`` of include/spt_hip.h."""
+    _fields_ = [
+        ('a2', _c_ptr), ('gather2', _c_ptr), ('b2', _c_ptr),
+        ('lda2', ctypes.c_int32), ('r', ctypes.c_int32),
+        ('b2_group_stride', ctypes.c_int64), ('b2_ldn', ctypes.c_int32),
+    ]
+
+
+def grouped_gemm_bf16_ext(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Tensor,
+                          n_groups: int, n: int, k: int, w_group_stride: int, w_ldn: int, w_ldk: int,
+                          a2: torch.Tensor, b2: torch.Tensor, b2_group_stride: int, gather2=None,
+                          n_rows: int = None, gather=None, bias=None, rowscale=None,
+                          epilogue: int = 0, activation: int = 0, keep_preact: bool = False,
+                          h_in=None, s_in=None, out: torch.Tensor = None, accumulate: bool = False,
+                          want_dots: bool = False):
+    """``spt_grouped_gemm_bf16_ext``: ``grouped_gemm_bf16`` plus the K extension
+    v[p, n] += a2[src2(p)] . b2_g(n) after rowscale and bias -- ``a2`` fp32 [*, r] (the LoRA down product),
+    ``b2`` bf16 [.., r] rows (``b2_group_stride`` elements apart per group, 0: one table).  Returns ``out``
+    (EPI_PLAIN), ``(out, preact | None)`` (EPI_ACT) or ``(out, dot_main, dot_act)`` (EPI_DACT with
+    ``want_dots``: the fp32 per-half-tile row dots, SptGroupedGemm.pdot_*)."""
+    for t, name in ((a, 'a'), (weight, 'weight'), (b2, 'b2')):
+        _check_type(t, torch.bfloat16, name)
+    _check_type(a2, torch.float32, 'a2')
+    _check_type(offsets, torch.int32, 'offsets')
+    _require(a.is_cuda and weight.is_cuda and offsets.is_cuda and a2.is_cuda and b2.is_cuda,
+             'grouped_gemm_bf16_ext needs CUDA tensors')
+    _require(a.dim() == 2 and a.stride(1) == 1, 'a must be [rows, k] with unit inner stride')
+    _require(weight.is_contiguous() and b2.is_contiguous(), 'weight and b2 must be contiguous')
+    _require(a2.dim() == 2 and a2.stride(1) == 1, 'a2 must be [rows, r] with unit inner stride')
+    _require(offsets.numel() == n_groups + 1, 'offsets must have n_groups + 1 entries')
+    r = a2.size(1)
+    _require(r % 4 == 0 and 0 < r <= 32 and a2.stride(0) % 4 == 0 and a2.data_ptr() % 16 == 0
+             and b2.data_ptr() % 8 == 0 and b2_group_stride % 4 == 0,
+             'grouped_gemm_bf16_ext: r % 4 == 0, r <= 32, 16-byte aligned a2 rows, 8-byte aligned b2')
+    _require(b2.numel() >= (n_groups - 1) * b2_group_stride + n * r, 'b2: [n_groups][n][r] rows')
+    dev = _same_device(a, weight, offsets, a2, b2)
+    if n_rows is None:
+        n_rows = gather.numel() if gather is not None else a.size(0)
+    for t, name in ((gather, 'gather'), (gather2, 'gather2')):
+        if t is not None:
+            _check_type(t, torch.int32, name)
+            _require(t.is_cuda and t.is_contiguous() and t.numel() >= n_rows, name + ': [n_rows] int32')
+    for t, name, dt in ((bias, 'bias', torch.bfloat16), (rowscale, 'rowscale', torch.float32),
+                        (h_in, 'h_in', torch.bfloat16), (s_in, 's_in', torch.bfloat16)):
+        if t is not None:
+            _check_type(t, dt, name)
+            _require(t.is_cuda and t.is_contiguous(), name + ' must be a contiguous CUDA tensor')
+    _require(grouped_gemm_bf16_supported(k, n, w_group_stride, w_ldn, w_ldk, a.stride(0))
+             and a.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0,
+             'grouped_gemm_bf16_ext: k % 64 == 0, 16-byte aligned rows of a and of the weight (include/spt_hip.h)')
+    lib = load_library()
+    with _on(dev):
+        _require(not accumulate or out is not None, 'accumulate: needs `out`')
+        if out is None:
+            out = torch.empty([n_rows, n], dtype=torch.bfloat16, device=dev)
+        else:
+            _check_type(out, torch.bfloat16, 'out')
+            _require(epilogue == EPI_PLAIN and out.is_cuda and out.dim() == 2 and out.stride(1) == 1
+                     and out.size(0) == n_rows and out.size(1) >= n,
+                     'out: [n_rows, >= n] bf16 with unit inner stride (EPI_PLAIN only)')
+        preact = torch.empty_like(out) if epilogue == EPI_ACT and keep_preact else None
+        dot_main = dot_act = None
+        pdot_ld = 0
+        if epilogue == EPI_DACT and want_dots:
+            pdot_ld = lib.spt_grouped_gemm_pdot_width(n)
+            dot_main = torch.empty([n_rows, pdot_ld], dtype=torch.float32, device=dev)
+            dot_act = torch.empty_like(dot_main)
+        if n_rows > 0:
+            desc = _GroupedDescBf16(
+                a=_ptr(a), gather=_ptr(gather), w=_ptr(weight), bias=_ptr(bias), rowscale=_ptr(rowscale),
+                offsets=_ptr(offsets), out=_ptr(out), n_rows=n_rows, k=k, n=n, n_groups=n_groups,
+                lda=a.stride(0), w_group_stride=w_group_stride, w_ldn=w_ldn, w_ldk=w_ldk, ldo=out.stride(0),
+                epilogue=epilogue, activation=activation, accumulate=int(bool(accumulate)),
+                out2=_ptr(preact), h_in=_ptr(h_in), s_in=_ptr(s_in), pdot_main=_ptr(dot_main),
+                pdot_act=_ptr(dot_act), pdot_ld=pdot_ld)
+            xdesc = _GroupedExtBf16(a2=a2.data_ptr(), gather2=_ptr(gather2), b2=b2.data_ptr(), lda2=a2.stride(0),
+                                    r=r, b2_group_stride=b2_group_stride, b2_ldn=r)
+            PATH_COUNTS[('grouped_gemm', 'bf16_ext')] += 1
+            rc = lib.spt_grouped_gemm_bf16_ext(ctypes.byref(desc), ctypes.byref(xdesc), _stream(dev))
+            if rc != 0:
+                _raise(lib, rc, 'grouped_gemm_bf16_ext')
+    if epilogue == EPI_ACT:
+        return out, preact
+    if epilogue == EPI_DACT and want_dots:
+        return out, dot_main, dot_act
+    return out
+
+
+def lora_down_bf16_supported(x: torch.Tensor, table: torch.Tensor) -> bool:
+    """x [rows, K] bf16 (K % 64 == 0, row stride % 8, 16-byte aligned); table [K, n] bf16 contiguous,
+    n % 4 == 0, n <= 64."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and table.dtype == torch.bfloat16 and x.dim() == 2
+            and table.dim() == 2 and x.stride(1) == 1 and x.size(0) > 0 and x.size(1) % 64 == 0
+            and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and table.is_contiguous()
+            and table.size(0) == x.size(1) and table.size(1) % 4 == 0 and 0 < table.size(1) <= 64
+            and table.data_ptr() % 8 == 0)
+
+
+def lora_down_bf16(x: torch.Tensor, table: torch.Tensor, block_major: bool = False) -> torch.Tensor:
+    """``spt_lora_down_bf16``: u = x @ table as FP32 [rows, n] (``block_major``: [n / 16, rows, 16]) from bf16
+    x and table -- exact products, fp32 accumulation."""
+    _require(lora_down_bf16_supported(x, table), 'lora_down_bf16: see lora_down_bf16_supported')
+    rows, k = x.shape
+    n = table.size(1)
+    _require(not block_major or n % 16 == 0, 'lora_down_bf16: block_major needs n % 16 == 0')
+    dev = _same_device(x, table)
+    lib = load_library()
+    with _on(dev):
+        u = torch.empty([n // 16, rows, 16] if block_major else [rows, n], dtype=torch.float32, device=dev)
+        rc = lib.spt_lora_down_bf16(x.data_ptr(), x.stride(0), rows, k, table.data_ptr(), n, u.data_ptr(), 0,
+                                    int(block_major), _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'lora_down_bf16')
+    return u
+
+
+def lora_down_grouped_bf16(x: torch.Tensor, tables: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """``spt_lora_down_grouped_bf16``: u[p] = x[p] @ tables[g(p)] (FP32 [rows, n]) for rows sorted by group
+    (offsets [G + 1] int32 on the device, offsets[G] == rows); tables [G, K, n] bf16, G <= 64."""
+    _require(tables.dim() == 3 and tables.is_contiguous() and 0 < tables.size(0) <= 64
+             and lora_down_bf16_supported(x, tables[0]), 'lora_down_grouped_bf16: see lora_down_bf16_supported')
+    _check_type(offsets, torch.int32, 'offsets')
+    G, k, n = tables.shape
+    _require(offsets.is_cuda and offsets.is_contiguous() and offsets.numel() == G + 1, 'offsets: [G + 1] int32')
+    rows = x.size(0)
+    dev = _same_device(x, tables, offsets)
+    lib = load_library()
+    with _on(dev):
+        u = torch.empty([rows, n], dtype=torch.float32, device=dev)
+        rc = lib.spt_lora_down_grouped_bf16(x.data_ptr(), x.stride(0), rows, k, tables.data_ptr(), k * n, n,
+                                            offsets.data_ptr(), G, u.data_ptr(), 0, _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'lora_down_grouped_bf16')
+    return u
+
+
+def tall_tn_bf16_supported(wide: torch.Tensor, narrow: torch.Tensor) -> bool:
+    return (wide.is_cuda and wide.dtype == torch.bfloat16 and narrow.dtype == torch.float32
+            and wide.dim() == 2 and narrow.dim() == 2 and wide.stride(1) == 1 and narrow.stride(1) == 1
+            and narrow.size(1) % 4 == 0 and 0 < narrow.size(1) <= 48 and wide.size(1) % 2 == 0
+            and wide.stride(0) % 2 == 0 and wide.data_ptr() % 4 == 0 and wide.size(0) > 0
+            and narrow.stride(0) % 4 == 0 and narrow.data_ptr() % 16 == 0)
+
+
+def tall_tn_bf16(wide: torch.Tensor, narrow: torch.Tensor, gather: torch.Tensor = None,
+                 offsets: torch.Tensor = None) -> torch.Tensor:
+    """``spt_tall_tn_bf16``: wide^T . narrow -> bf16 [G, width, n] for a bf16 ``wide`` and an fp32 ``narrow``,
+    each element rounded once after the in-order reduction (bitwise reproducible); gather / offsets as
+    ``tall_tn``."""
+    _require(tall_tn_bf16_supported(wide, narrow), 'tall_tn_bf16: bf16 CUDA [rows, even width] x fp32 [*, n % 4, <= 48]')
+    rows, width = wide.shape
+    n = narrow.size(1)
+    G = 1 if offsets is None else offsets.numel() - 1
+    if gather is not None:
+        _check_type(gather, torch.int32, 'gather')
+        _require(gather.is_contiguous() and gather.numel() == rows, 'gather: one int32 per row of wide')
+    else:
+        _require(narrow.size(0) == rows, 'narrow: one row per row of wide')
+    if offsets is not None:
+        _check_type(offsets, torch.int32, 'offsets')
+        _require(offsets.is_contiguous() and G >= 1, 'offsets: [G + 1] int32')
+    dev = _same_device(wide, narrow)
+    lib = load_library()
+    with _on(dev):
+        out = torch.empty([G, width, n], dtype=torch.bfloat16, device=dev)
+        work = torch.empty([lib.spt_tall_tn_bf16_workspace_bytes(rows, G, width, n)], dtype=torch.uint8, device=dev)
+        rc = lib.spt_tall_tn_bf16(wide.data_ptr(), wide.stride(0), narrow.data_ptr(), narrow.stride(0),
+                                  _ptr(gather), _ptr(offsets), G, rows, width, n, out.data_ptr(),
+                                  work.data_ptr(), _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'tall_tn_bf16')
+    return out
+
+
+def swiglu_backward_dots_bf16(dh: torch.Tensor, g: torch.Tensor, s: torch.Tensor):
+    """``spt_swiglu_backward_dots_bf16``: -> (dg, ds) bf16 and the fp32 row dots (dot_h, dot_g, dot_s) of the
+    stored values, as ``swiglu_backward`` returns them."""
+    _require(swiglu_bf16_supported(g, s) and g.dim() == 2 and g.size(1) % 4 == 0 and dh.shape == g.shape
+             and dh.dtype == torch.bfloat16 and dh.is_contiguous() and dh.device == g.device
+             and dh.data_ptr() % 8 == 0, 'swiglu_backward_dots_bf16: contiguous bf16 CUDA [rows, n % 4 == 0]')
+    rows, n = g.shape
+    dev = g.device
+    lib = load_library()
+    with _on(dev):
+        dg, ds = torch.empty_like(g), torch.empty_like(g)
+        dots = torch.empty([3, rows], dtype=torch.float32, device=dev)
+        rc = lib.spt_swiglu_backward_dots_bf16(dh.data_ptr(), g.data_ptr(), s.data_ptr(), dg.data_ptr(),
+                                               ds.data_ptr(), dots.data_ptr(), rows, n, _stream(dev))
+    if rc != 0:
+        _raise(lib, rc, 'swiglu_backward_dots_bf16')
+    return dg, ds, dots[0], dots[1], dots[2]

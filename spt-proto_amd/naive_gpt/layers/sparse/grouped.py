@@ -18,7 +18,9 @@ bucket rows (``spt_grouped_gemm_wgrad``), written straight into the parameters' 
 bf16 storage (the plain routed FFNs whose activations and weights are ALL bf16): the same bucketing
 (the router's probabilities widened to fp32 for it) and the bf16 kernels -- ``spt_grouped_gemm_bf16``,
 ``spt_grouped_gemm_wgrad_bf16``, ``spt_rows_combine_bf16``, ``spt_swiglu_*_bf16``: fp32 accumulation of
-the exact products of the stored bf16 values, each result rounded once when stored.
+the exact products of the stored bf16 values, each result rounded once when stored.  The LoRA routed
+FFNs in bf16 (RoutedLoRAFFNBf16 / RoutedLoRALLaMAFFNBf16, opt-in through LORA_BF16) add the K extension
+(``spt_grouped_gemm_bf16_ext``), ``spt_lora_down*_bf16`` and ``spt_tall_tn_bf16``, with fp32 rank-r sides.
 """
 import os
 from typing import NamedTuple
@@ -375,8 +377,8 @@ def usable(x: torch.Tensor, *frozen_weights) -> bool:
 
 
 def bf16_usable(x: torch.Tensor, *frozen_weights) -> bool:
-    """The bf16 grouped path of the PLAIN routed FFNs (feedforward.py; the LoRA routed variants keep
-    the fp32 gate above): bf16 CUDA activations and frozen bf16 base weights, every one of them."""
+    """The bf16 grouped path of the PLAIN routed FFNs (feedforward.py; the LoRA routed variants have their
+    own, lora_bf16_usable): bf16 CUDA activations and frozen bf16 base weights, every one of them."""
     if not x.is_cuda or x.dtype != torch.bfloat16:
         return False
     for w in frozen_weights:
@@ -933,3 +935,265 @@ def routed_lora_llama_ffn(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_block
                                         activation)
     return RoutedLoRALLaMAFFN.apply(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks, top_k,
                                     activation, origin.input, origin.module)
+
+
+# ---------------------------------------------------------------- the LoRA routed FFNs on bf16 storage
+# The fused bf16 path of LoRARoutedFFN / LoRARoutedLLaMaFFN (tuning/lora_ffn.py): opt-in until it is measured
+# as the default; read at call time (tests flip it).
+LORA_BF16 = os.environ.get('SPT_ROUTED_LORA_BF16', '0') != '0'
+
+
+def lora_bf16_unusable(x: torch.Tensor, rank: int, plain_router: bool, d: int, bs: int, frozen, trained):
+    """None when the fused bf16 LoRA path takes these operands, else the reason it does not: the flag,
+    bf16 CUDA activations, frozen contiguous bf16 base weights (`frozen`, None entries skipped), bf16
+    contiguous LoRA tables and router (`trained`), d and the block size multiples of 64, a rank the
+    K extension takes and a plain Linear + Sigmoid router."""
+    if not LORA_BF16:
+        return 'SPT_ROUTED_LORA_BF16 is off'
+    if not x.is_cuda or x.dtype != torch.bfloat16:
+        return 'x {} {}: bf16 CUDA activations only'.format(tuple(x.shape), x.dtype)
+    for w in frozen:
+        if w is None:
+            continue
+        if w.requires_grad or not w.is_cuda or not w.is_contiguous() or w.dtype != torch.bfloat16:
+            return 'base weight {} {}: frozen contiguous bf16 CUDA weights only'.format(tuple(w.shape), w.dtype)
+    for t in trained:
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.bfloat16:
+            return 'LoRA table / router {} {}: contiguous bf16 CUDA tensors only'.format(tuple(t.shape), t.dtype)
+    if not bf16_shapes(d, bs):
+        return 'd {} block {}: multiples of 64 only'.format(d, bs)
+    if not fused_usable(rank):
+        return 'rank {}: rank % 4 == 0 and rank <= 32 only'.format(rank)
+    if not plain_router:
+        return 'router: Linear + Sigmoid only'
+    return None
+
+
+def lora_bf16_usable(x: torch.Tensor, rank: int, plain_router: bool, d: int, bs: int, frozen, trained) -> bool:
+    return lora_bf16_unusable(x, rank, plain_router, d, bs, frozen, trained) is None
+
+
+def _route_bf16(x: torch.Tensor, rw: torch.Tensor, rb: torch.Tensor, n_blocks: int, k: int):
+    """The router as the bf16 module computes it (Linear + Sigmoid in bf16), its probabilities widened to
+    fp32 for the bucketing: -> (prob fp32 [T, nb], Buckets with coeff = 2 prob, block ids int32 [P])."""
+    prob = torch.sigmoid(torch.nn.functional.linear(x, rw, rb)).float()
+    if ext.route_topk_supported(prob.size(0), n_blocks):
+        ext.note_path('route_topk', 'kernel')
+        token, block, offsets, pos, token_long, block_long, coeff = ext.route_topk_coeff(prob, k, 2.0)
+        return prob, Buckets(token=token, token_long=token_long, block=block_long, offsets=offsets,
+                             coeff=coeff, n_blocks=n_blocks, pos=pos), block
+    bk = make_buckets(prob, k, scale=2.0)
+    return prob, bk, bk.block.int()
+
+
+def _route_backward_bf16(ctx, grad_coeff, prob, bk: Buckets, block, x, rw, grad_x):
+    """_route_backward for the bf16 router: d logit in fp32, its share of the input gradient added to the
+    bf16 `grad_x` (a second rounding of grad_x), the router's gradients rounded once to its dtype.
+    -> (grad_x, grad_rw, grad_rb)."""
+    nb = bk.n_blocks
+    if grad_coeff.is_cuda and nb <= 8:
+        dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
+    else:
+        dprob = torch.zeros_like(prob)
+        dprob.view(-1).index_put_((bk.token_long * nb + bk.block,), 2.0 * grad_coeff)
+        dlogit = dprob * (1.0 - prob) * prob
+    grad_x = torch.addmm(grad_x.float(), dlogit, rw.float()).to(grad_x.dtype)
+    grad_rw = torch.matmul(dlogit.t(), x.float()).to(rw.dtype) if ctx.needs_input_grad[1] else None
+    grad_rb = dlogit.sum(dim=0).to(rw.dtype) if ctx.needs_input_grad[2] else None
+    return grad_x, grad_rw, grad_rb
+
+
+def _tables(table: torch.Tensor, nb: int) -> torch.Tensor:
+    """[nb * bs, r] -> [nb, bs, r]"""
+    return table.view(nb, table.size(0) // nb, table.size(1))
+
+
+class RoutedLoRAFFNBf16(torch.autograd.Function):
+    """RoutedLoRAFFN on bf16 storage (x, base weights, LoRA tables, router, h, s and the gradients bf16; the
+    rank-r intermediates u, z, dzt, du fp32):
+
+        u  = x L1                                              spt_lora_down_bf16
+        h  = act(c (x W1_g^T + b1_g) + u R1_g^T)               spt_grouped_gemm_bf16_ext, EPI_ACT
+        z  = h L2_g;  ys = c (h W2_g) + z R2^T                 spt_lora_down_grouped_bf16, _bf16_ext
+        y  = b2 + sum over the token's rows of ys              spt_rows_combine_bf16
+      backward
+        dzt = dy R2;  ds = (c (dy W2_g^T) + dzt L2_g^T) * act'(s), + the row dots     EPI_DACT
+        du = ds R1_g;  dx = sum over the token's rows of c (ds W1_g) + du L1^T
+        LoRA table gradients                                   spt_tall_tn_bf16
+
+    The router is the module's bf16 Linear + Sigmoid; its probabilities are widened to fp32 for the
+    bucketing and the coefficient gradient; d logit . W_r is added to dx by torch."""
+
+    @staticmethod
+    def forward(ctx, x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, nb: int, top_k: int, act: int,
+                origin_input=None, origin_module=None):
+        d_ff, d = w1.shape
+        x = x.contiguous()
+        bs, rank = d_ff // nb, l1.size(1)
+        relu = act == ext.ACT_RELU
+        prob, bk, block = _route_bf16(x, rw, rb, nb, top_k)
+        coeff, rows = bk.coeff, bk.token.numel()
+        u = ext.lora_down_bf16(x, l1)                                        # [T, r] fp32
+        h, s = ext.grouped_gemm_bf16_ext(
+            x, w1, bk.offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1, n_rows=rows,
+            gather=bk.token, bias=b1.view(nb, bs), rowscale=coeff, a2=u, gather2=bk.token, b2=r1,
+            b2_group_stride=bs * rank, epilogue=ext.EPI_ACT, activation=act, keep_preact=not relu)
+        z = ext.lora_down_grouped_bf16(h, _tables(l2, nb), bk.offsets)       # [P, r] fp32
+        ys = ext.grouped_gemm_bf16_ext(
+            h, w2, bk.offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1, n_rows=rows,
+            rowscale=coeff, a2=z, b2=r2, b2_group_stride=0)
+        y = ext.rows_combine(ys, bk.pos, bias=b2)
+        ctx.bk, ctx.act = bk, act
+        ctx.origin_module = origin_module
+        ctx.save_for_backward(x if origin_module is None else origin_input, coeff, u, h, s, z,
+                              l1, r1, l2, r2, w1, w2, prob, block, rw)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, coeff, u, h, s, z, l1, r1, l2, r2, w1, w2, prob, block, rw = ctx.saved_tensors
+        if ctx.origin_module is not None:
+            x = recompute.output(ctx.origin_module, x).view(-1, w1.size(1))
+        bk, act = ctx.bk, ctx.act
+        nb = bk.n_blocks
+        d_ff, d = w1.shape
+        bs, rank, rows = d_ff // nb, l1.size(1), bk.token.numel()
+        dy = dy.contiguous()
+        dzt = ext.lora_down_bf16(dy, r2)                                     # [T, r] fp32
+        ds, dot_main, dot_act = ext.grouped_gemm_bf16_ext(
+            dy, w2, bk.offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff, n_rows=rows,
+            gather=bk.token, rowscale=coeff, a2=dzt, gather2=bk.token, b2=l2, b2_group_stride=bs * rank,
+            epilogue=ext.EPI_DACT, activation=act, h_in=h, s_in=s, want_dots=True)
+        du = ext.lora_down_grouped_bf16(ds, _tables(r1, nb), bk.offsets)     # [P, r] fp32
+        # (dot_main + dot_act - <du, u[token]> - <dzt[token], z>) / c: RoutedLoRAFFN.backward
+        grad_coeff = ext.ffn_coeff_grad(dot_main, dot_act, du, u, dzt, z, bk.token, coeff, COEFF_FLOOR)
+        del dot_main, dot_act
+        grad_l1 = ext.tall_tn_bf16(x, ext.rows_combine(du, bk.pos)).view(d, rank)
+        grad_r2 = ext.tall_tn_bf16(dy, ext.rows_combine(z, bk.pos)).view(d, rank)
+        grad_r1 = ext.tall_tn_bf16(ds, u, gather=bk.token, offsets=bk.offsets).view(d_ff, rank)
+        grad_l2 = ext.tall_tn_bf16(h, dzt, gather=bk.token, offsets=bk.offsets).view(d_ff, rank)
+        dxs = ext.grouped_gemm_bf16_ext(
+            ds, w1, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d, n_rows=rows,
+            rowscale=coeff, a2=du, b2=l1, b2_group_stride=0)
+        del ds, du
+        grad_x = ext.rows_combine(dxs, bk.pos)
+        del dxs
+        grad_x, grad_rw, grad_rb = _route_backward_bf16(ctx, grad_coeff, prob, bk, block, x, rw, grad_x)
+        return (grad_x, grad_rw, grad_rb, grad_l1, grad_r1, grad_l2, grad_r2,
+                None, None, None, None, None, None, None, None, None)
+
+
+def routed_lora_ffn_bf16(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks: int, top_k: int, act: int,
+                         origin=None):
+    if origin is None:
+        return RoutedLoRAFFNBf16.apply(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks, top_k, act)
+    return RoutedLoRAFFNBf16.apply(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks, top_k, act,
+                                   origin.input, origin.module)
+
+
+class RoutedLoRALLaMAFFNBf16(torch.autograd.Function):
+    """RoutedLoRALLaMAFFN on bf16 storage (see RoutedLoRAFFNBf16; ug, us, z, dzt and the du's fp32):
+
+        g  = c (x G_g^T) + ug Rg_g^T,  sd = c (x S_g^T) + us Rs_g^T     two spt_grouped_gemm_bf16_ext
+        h  = silu(g) * sd                                               spt_swiglu_forward_bf16
+        ys = c (h D_g) + (h Ld_g) Rd^T;  y = sum over the token's rows of ys
+      backward: dh through the same GEMM, spt_swiglu_backward_dots_bf16 for dg, dsd and the row dots of
+      the coefficient gradient, the two dX products accumulated into one bf16 buffer."""
+
+    @staticmethod
+    def forward(ctx, x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, nb: int, top_k: int, activation,
+                origin_input=None, origin_module=None):
+        d_ff, d = wg.shape
+        x = x.contiguous()
+        prob, bk, block = _route_bf16(x, rw, rb, nb, top_k)
+        coeff = bk.coeff
+        bs, rank, rows = d_ff // nb, lg.size(1), bk.token.numel()
+        # one pass over x for both adapters: [T, 2 r], ug | us side by side
+        ugs = ext.lora_down_bf16(x, torch.cat([lg, ls], dim=1))
+        ug, us = ugs[:, :rank], ugs[:, rank:]
+
+        def up(w, u, r_table):
+            return ext.grouped_gemm_bf16_ext(
+                x, w, bk.offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1, n_rows=rows,
+                gather=bk.token, rowscale=coeff, a2=u, gather2=bk.token, b2=r_table, b2_group_stride=bs * rank)
+
+        g, sd = up(wg, ug, rg), up(ws, us, rs)
+        silu = isinstance(activation, torch.nn.SiLU) and ext.swiglu_bf16_supported(g, sd)
+        ext.note_path('swiglu', 'kernel_bf16' if silu else 'torch', fallback=not silu,
+                      why=lambda: 'activation {} on {}'.format(type(activation).__name__, tuple(g.shape)))
+        h = ext.swiglu_forward_bf16(g, sd) if silu else activation(g) * sd
+        z = ext.lora_down_grouped_bf16(h, _tables(ld, nb), bk.offsets)       # [P, r] fp32
+        ys = ext.grouped_gemm_bf16_ext(
+            h, wd, bk.offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1, n_rows=rows,
+            rowscale=coeff, a2=z, b2=rd, b2_group_stride=0)
+        y = ext.rows_combine(ys, bk.pos)
+        ctx.bk, ctx.activation, ctx.silu = bk, activation, silu
+        ctx.origin_module = origin_module
+        ctx.save_for_backward(x if origin_module is None else origin_input, coeff, ugs, g, sd, h, z,
+                              lg, rg, ls, rs, ld, rd, wg, ws, wd, prob, block, rw)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x, coeff, ugs, g, sd, h, z, lg, rg, ls, rs, ld, rd, wg, ws, wd, prob, block,
+         rw) = ctx.saved_tensors
+        if ctx.origin_module is not None:
+            x = recompute.output(ctx.origin_module, x).view(-1, wg.size(1))
+        bk, activation = ctx.bk, ctx.activation
+        nb = bk.n_blocks
+        d_ff, d = wg.shape
+        bs, rank, rows = d_ff // nb, lg.size(1), bk.token.numel()
+        ug, us = ugs[:, :rank], ugs[:, rank:]
+        dy = dy.contiguous()
+        dzt = ext.lora_down_bf16(dy, rd)                                     # [T, r] fp32
+        dh = ext.grouped_gemm_bf16_ext(
+            dy, wd, bk.offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff, n_rows=rows,
+            gather=bk.token, rowscale=coeff, a2=dzt, gather2=bk.token, b2=ld, b2_group_stride=bs * rank)
+        if ctx.silu:
+            dg, dsd, dot_h, dot_g, dot_s = ext.swiglu_backward_dots_bf16(dh, g, sd)
+        else:
+            with torch.enable_grad():
+                g_ = g.detach().requires_grad_(True)
+                ag = activation(g_)
+                dg, = torch.autograd.grad(ag, g_, dh * sd)
+            dsd = dh * ag.detach()
+            dot_h = (dh.float() * h.float()).sum(dim=-1)
+            dot_g = (dg.float() * g.float()).sum(dim=-1)
+            dot_s = (dsd.float() * sd.float()).sum(dim=-1)
+            del ag, g_
+        del dh
+        dz_rows = dzt.index_select(0, bk.token_long)
+        grad_coeff = (dot_h - (dz_rows * z).sum(dim=-1)) / _floor(coeff)
+
+        def down(dpre, w, u, l_table, r_table, dot_pre, into=None):
+            """-> (dx rows [P, d] bf16, d coefficient [P], grad of the two LoRA tables)"""
+            du = ext.lora_down_grouped_bf16(dpre, _tables(r_table, nb), bk.offsets)
+            dc = (dot_pre - (du * u.index_select(0, bk.token_long)).sum(dim=-1)) / _floor(coeff)
+            dxs = ext.grouped_gemm_bf16_ext(
+                dpre, w, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d, n_rows=rows,
+                rowscale=coeff, a2=du, b2=l_table, b2_group_stride=0, out=into, accumulate=into is not None)
+            grad_l = ext.tall_tn_bf16(x, ext.rows_combine(du, bk.pos)).view(d, rank)
+            grad_r = ext.tall_tn_bf16(dpre, u, gather=bk.token, offsets=bk.offsets).view(d_ff, rank)
+            return dxs, dc, grad_l, grad_r
+
+        dxs, dc_g, grad_lg, grad_rg = down(dg, wg, ug, lg, rg, dot_g)
+        del dg
+        dxs, dc_s, grad_ls, grad_rs = down(dsd, ws, us, ls, rs, dot_s, into=dxs)
+        del dsd
+        grad_x = ext.rows_combine(dxs, bk.pos)
+        del dxs
+        grad_coeff = grad_coeff + dc_g + dc_s
+        grad_x, grad_rw, grad_rb = _route_backward_bf16(ctx, grad_coeff, prob, bk, block, x, rw, grad_x)
+        grad_ld = ext.tall_tn_bf16(h, dzt, gather=bk.token, offsets=bk.offsets).view(d_ff, rank)
+        grad_rd = ext.tall_tn_bf16(dy, ext.rows_combine(z, bk.pos)).view(d, rank)
+        return (grad_x, grad_rw, grad_rb, grad_lg, grad_rg, grad_ls, grad_rs, grad_ld, grad_rd,
+                None, None, None, None, None, None, None, None)
+
+
+def routed_lora_llama_ffn_bf16(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks: int, top_k: int,
+                               activation, origin=None):
+    if origin is None:
+        return RoutedLoRALLaMAFFNBf16.apply(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks, top_k,
+                                            activation)
+    return RoutedLoRALLaMAFFNBf16.apply(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks, top_k,
+                                        activation, origin.input, origin.module)

@@ -108,6 +108,17 @@ class LoRARoutedFFN(layers.RoutedFFN):
         y = torch.zeros_like(x).index_add_(0, bk.token_long, ys)
         return y + self.fc2.bias.view([1, -1])
 
+    def _bf16_unusable(self, x: torch.Tensor):
+        """why the fused bf16 path does not take this call (None: it does)"""
+        if grouped.activation_code(self.activation) is None:
+            return 'activation {}: ReLU, exact GELU or SiLU only'.format(type(self.activation).__name__)
+        router = self.router[0] if _plain_router(self.router) else None
+        return grouped.lora_bf16_unusable(
+            x, self.fc1.lora.left.weight.size(1), router is not None, self.d_model, self.block_size,
+            (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias),
+            (self.fc1.lora.left.weight, self.fc1.lora.right.weight, self.fc2.lora.left.weight,
+             self.fc2.lora.right.weight) + ((router.weight, router.bias) if router is not None else ()))
+
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         origin = recompute.origin_of(x) if x.is_contiguous() else None
@@ -115,9 +126,23 @@ class LoRARoutedFFN(layers.RoutedFFN):
         if grouped.usable(x, self.fc1.weight, self.fc1.bias, self.fc2.weight) \
                 and self.d_model % 4 == 0 and self.block_size % 4 == 0:
             return self._forward_grouped(x.contiguous(), origin).view(x_size)
-        ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda,
-                      why=lambda: 'x {} {}: the grouped GEMMs take fp32 CUDA activations and frozen base weights'.format(
-                          tuple(x.shape), x.dtype))
+        why_bf16 = self._bf16_unusable(x) if grouped.LORA_BF16 and x.dtype == torch.bfloat16 else 'off'
+        if why_bf16 is None:
+            # the fused path on bf16 storage (layers/sparse/grouped.py: RoutedLoRAFFNBf16)
+            ext.note_path('routed_ffn', 'fused_bf16')
+            nb = self.n_blocks
+            return grouped.routed_lora_ffn_bf16(
+                x.contiguous(), self.router[0].weight, self.router[0].bias,
+                self.fc1.lora.left.weight, self.fc1.lora.right.weight,
+                self.fc2.lora.left.weight, self.fc2.lora.right.weight,
+                self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, nb, nb // 2,
+                grouped.activation_code(self.activation), origin=origin).view(x_size)
+        if why_bf16 != 'off':
+            ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda, why=lambda: 'bf16: ' + why_bf16)
+        else:
+            ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda,
+                          why=lambda: 'x {} {}: the grouped GEMMs take fp32 CUDA activations and frozen base weights'.format(
+                              tuple(x.shape), x.dtype))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 2)
 
@@ -203,6 +228,15 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
         ys = y2 + torch.matmul(z, self.down.lora.right.weight.T)
         return torch.zeros_like(x).index_add_(0, bk.token_long, ys)
 
+    def _bf16_unusable(self, x: torch.Tensor):
+        """why the fused bf16 path does not take this call (None: it does)"""
+        router = self.router[0] if _plain_router(self.router) else None
+        return grouped.lora_bf16_unusable(
+            x, self.gate.lora.left.weight.size(1), router is not None, self.d_model, self.block_size,
+            (self.gate.weight, self.side.weight, self.down.weight),
+            tuple(t for lin in (self.gate, self.side, self.down) for t in (lin.lora.left.weight, lin.lora.right.weight))
+            + ((router.weight, router.bias) if router is not None else ()))
+
     def forward(self, x: torch.Tensor):
         x_size = x.size()
         origin = recompute.origin_of(x) if x.is_contiguous() else None
@@ -210,9 +244,24 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
         if grouped.usable(x, self.gate.weight, self.side.weight, self.down.weight) \
                 and self.d_model % 4 == 0 and self.block_size % 4 == 0:
             return self._forward_grouped(x.contiguous(), origin).view(x_size)
-        ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda,
-                      why=lambda: 'x {} {}: the grouped GEMMs take fp32 CUDA activations and frozen base weights'.format(
-                          tuple(x.shape), x.dtype))
+        why_bf16 = self._bf16_unusable(x) if grouped.LORA_BF16 and x.dtype == torch.bfloat16 else 'off'
+        if why_bf16 is None:
+            # the fused path on bf16 storage (layers/sparse/grouped.py: RoutedLoRALLaMAFFNBf16)
+            ext.note_path('routed_ffn', 'fused_bf16')
+            nb = self.n_blocks
+            return grouped.routed_lora_llama_ffn_bf16(
+                x.contiguous(), self.router[0].weight, self.router[0].bias,
+                self.gate.lora.left.weight, self.gate.lora.right.weight,
+                self.side.lora.left.weight, self.side.lora.right.weight,
+                self.down.lora.left.weight, self.down.lora.right.weight,
+                self.gate.weight, self.side.weight, self.down.weight, nb, nb // 2, self.activation,
+                origin=origin).view(x_size)
+        if why_bf16 != 'off':
+            ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda, why=lambda: 'bf16: ' + why_bf16)
+        else:
+            ext.note_path('routed_ffn', 'torch_loop', fallback=x.is_cuda,
+                          why=lambda: 'x {} {}: the grouped GEMMs take fp32 CUDA activations and frozen base weights'.format(
+                              tuple(x.shape), x.dtype))
         prob = self.router(x)
         route = routing.route_topk(prob, k=self.n_blocks // 2)
 

@@ -56,13 +56,11 @@ constexpr int MA_THREADS = MA_THREADS_VALUE;       // 512 or 256
 constexpr int MA_WAVES = MA_THREADS / SPT_WAVE;    // 8 or 4
 constexpr int MA_E = MA_E_VALUE;                   // d_head: 64 or 128
 constexpr int MA_EQ = MA_E / 4;                    // float4 per row of a tile
-constexpr int MA_RPT = 32 * MA_EQ / MA_THREADS;    // 32 x E tile: float4s per thread to stage
-constexpr int MA_RPP = MA_THREADS / MA_EQ;         // tile rows covered by one float4 per thread
 constexpr int MA_KS = MA_E / 16;                   // k-steps of a contraction over e
 constexpr int MA_ET = MA_E / 32;                   // 32-column tiles of an [*, E] result
 constexpr int MA_BH = MA_E / 64;                   // backward launches: 64 gradient columns each
 constexpr int MA_WROWS = 32;                       // rows per wave = one MFMA tile
-constexpr int MA_ROWS = MA_WAVES * MA_WROWS;       // 256 rows per workgroup
+constexpr int MA_ROWS = MA_WAVES * MA_WROWS;       // 256 rows per workgroup (the forward)
 constexpr int MA_KT = 32;                          // keys per tile
 [[maybe_unused]] constexpr int MA_MAXZ = 256;      // entries per row (cell counts are bytes)
 [[maybe_unused]] constexpr int MA_MAXNT = 64;      // key tiles: S <= 2048
@@ -197,12 +195,18 @@ __device__ __forceinline__ void put_cols4(char *img, int e, int r4, const float4
 }
 
 // Key tiles of the forward and of the row-owned backward: K rows image | V rows image (each
-// hi, lo).  Thread t stages the four elements (row t / (E/4) + MA_RPP u, columns 4 (t % (E/4)) ..)
-// for u < MA_RPT.
-template <typename T>
-struct TileRegs { typename Elem<T>::raw4 kf[MA_RPT], vf[MA_RPT]; };
-template <typename T>
+// hi, lo).  With NT threads staging, thread t stages the four elements (row t / (E/4) + RPP u,
+// columns 4 (t % (E/4)) ..) for u < RPT.
+template <int NT>
+struct Share {
+    static constexpr int RPT = 32 * MA_EQ / NT;      // 32 x E tile: float4s per thread to stage
+    static constexpr int RPP = NT / MA_EQ;           // tile rows covered by one float4 per thread
+};
+template <typename T, int NT = MA_THREADS>
+struct TileRegs { typename Elem<T>::raw4 kf[Share<NT>::RPT], vf[Share<NT>::RPT]; };
+template <typename T, int NT = MA_THREADS>
 struct TileStager {
+    static constexpr int RPT = Share<NT>::RPT, RPP = Share<NT>::RPP;
     const T *k_b, *v_b;
     int ld, S, jl, e4;
     __device__ __forceinline__ TileStager(const T *k, const T *v, int ld_, int S_, int tid)
@@ -211,28 +215,28 @@ struct TileStager {
     // with vmcnt(0) for OLDER loads too (it cannot count what the branch issued), which
     // exposed the full memory latency in every iteration.  Keys >= S read row S - 1: finite
     // data whose cells have multiplicity 0.
-    __device__ __forceinline__ TileRegs<T> load(int t) const {
-        TileRegs<T> r;
+    __device__ __forceinline__ TileRegs<T, NT> load(int t) const {
+        TileRegs<T, NT> r;
 #pragma unroll
-        for (int u = 0; u < MA_RPT; u++) {
-            const int j = min(t * MA_KT + jl + MA_RPP * u, S - 1);
+        for (int u = 0; u < RPT; u++) {
+            const int j = min(t * MA_KT + jl + RPP * u, S - 1);
             r.kf[u] = ld_raw4(k_b + (size_t)j * ld + e4);
             r.vf[u] = ld_raw4(v_b + (size_t)j * ld + e4);
         }
         return r;
     }
-    __device__ __forceinline__ void store(char *buf, const TileRegs<T> &r) const {
+    __device__ __forceinline__ void store(char *buf, const TileRegs<T, NT> &r) const {
 #pragma unroll
-        for (int u = 0; u < MA_RPT; u++) {
-            put_rows4(buf + MA_KH, jl + MA_RPP * u, e4, r.kf[u]);
-            put_rows4(buf + MA_VH, jl + MA_RPP * u, e4, r.vf[u]);
+        for (int u = 0; u < RPT; u++) {
+            put_rows4(buf + MA_KH, jl + RPP * u, e4, r.kf[u]);
+            put_rows4(buf + MA_VH, jl + RPP * u, e4, r.vf[u]);
         }
     }
     // max over this thread's K rows of the tile of the sum of squares of its four columns
-    __device__ __forceinline__ float k_share(const TileRegs<T> &r) const {
+    __device__ __forceinline__ float k_share(const TileRegs<T, NT> &r) const {
         float best = 0.f;
 #pragma unroll
-        for (int u = 0; u < MA_RPT; u++) {
+        for (int u = 0; u < RPT; u++) {
             const float4 x = Elem<T>::f4(r.kf[u]);
             best = fmaxf(best, fmaf(x.x, x.x, fmaf(x.y, x.y, fmaf(x.z, x.z, x.w * x.w))));
         }
@@ -1130,6 +1134,58 @@ void attention_mfma_forward_kernel(
 //   grad_q[i] = sum_j dS[i, j] k[j]     grad_k[j] = sum_i dS[i, j] q[i]     (kernels/sddmm.py)
 //   grad_v[j] = sum_i P[i, j] dY[i]     dP[i, j]  = dY[i] . v[j]            (kernels/spmm.py)
 
+// ---- the backward's workgroup shape ----
+// Both kernels need a 256-register budget (2 waves per SIMD).  At 8 waves per workgroup that is one
+// workgroup per CU (LDS alone: 102,400 / 119,040 B), and its barriers keep every wave of the CU in
+// the same phase -- loads, then MFMA, then VALU, nothing overlapping.  At d_head
+// 64 the backward therefore runs 4-wave workgroups of 128 rows (keys): 2 x 69,632 / 78,080 B of LDS
+// and 2 x 4 waves at 256 registers fit a CU, and the two workgroups' barriers are independent, so
+// one stages its next tile while the other multiplies.  d_head 128 keeps the 8-wave shape: its
+// kernels already spill at 256 registers, and half the threads would double each one's staging share.
+#if MA_E_VALUE == 64
+constexpr int BW_THREADS = 256;
+#else
+constexpr int BW_THREADS = MA_THREADS;
+#endif
+constexpr int BW_WAVES = BW_THREADS / SPT_WAVE;     // 4 (d_head 64) or 8
+constexpr int BW_ROWS = BW_WAVES * MA_WROWS;        // rows (keys) per workgroup: 128 or 256
+constexpr int BW_RPT = Share<BW_THREADS>::RPT, BW_RPP = Share<BW_THREADS>::RPP;
+// Which 32-row (32-key) tiles a backward workgroup owns: wave w of block g of its slice takes tile
+// BW_WAVES g + w.  Block g of the row-owned kernel walks BW_WAVES (g + 1) key tiles and block g of
+// the key-owned one RT - BW_WAVES g row tiles, so at S = 512 a slice's blocks carry 1 : 2 : 3 : 4
+// (rows) or 4 : 3 : 2 : 1 (keys) of the work.  blockIdx is therefore taken as rank * slices + slice,
+// rank 0 being the HEAVIEST block: every slice's longest block is dispatched first, and the short
+// ones fill the slots the long ones leave (1,024 workgroups on 512 slots at the bench shape, with
+// no half-empty third round).  Consecutive ids go round-robin to the eight XCDs, so with a slice
+// count divisible by 8 all blocks of a slice share one XCD's L2.  The 8-wave shape keeps the folded
+// mapping of the forward (one short and one long wave per SIMD: a CU holds one workgroup).
+struct BwBlock {
+    int b, g;            // slice, block of the slice
+    int tile;            // this wave's row (key) tile
+    int first, last;     // the smallest and the largest tile of the workgroup's waves
+};
+__device__ __forceinline__ BwBlock bw_block(int blocks_per_batch, int wave, bool heavy_last) {
+    BwBlock r;
+    if constexpr (BW_WAVES == MA_WAVES) {
+        const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
+        r.b = bid / blocks_per_batch;
+        r.g = bid % blocks_per_batch;
+        r.tile = folded_row_tile(r.g, blocks_per_batch, wave);
+        r.first = (MA_WAVES / 2) * r.g;
+        r.last = folded_row_tile(r.g, blocks_per_batch, MA_WAVES - 1);
+    } else {
+        const unsigned slices = gridDim.x / blocks_per_batch, rank = blockIdx.x / slices;
+        r.b = blockIdx.x - rank * slices;
+        r.g = heavy_last ? blocks_per_batch - 1 - (int)rank : (int)rank;
+        r.tile = BW_WAVES * r.g + wave;
+        r.first = BW_WAVES * r.g;
+        r.last = r.first + BW_WAVES - 1;
+    }
+    return r;
+}
+// The exact clamp guard reads the bounds the FORWARD's workgroups left: one slot per forward block.
+__device__ __forceinline__ int forward_slots(int S) { return (S + MA_ROWS - 1) / MA_ROWS; }
+
 // ---- row-owned: same skeleton as the forward and the same images, K rows | V rows (the K
 // rows image also feeds grad_q = dS^T K through the transposing read).
 // Measured by compiling phases out (80 us whole): without the tile arithmetic 54 us (prologue --
@@ -1137,10 +1193,11 @@ void attention_mfma_forward_kernel(
 // arithmetic but without the loop's loads, stores and barriers 75 us.  So the loop's memory
 // traffic hides behind the arithmetic, and the arithmetic (46 us for 16 us of MFMA-pipe time) is
 // one wave per SIMD running its MFMA and VALU phases one after the other: at 187 VGPRs a CU holds
-// one workgroup, and half of its waves (the short row tiles) finish early. ----
+// one workgroup, and half of its waves (the short row tiles) finish early.  (That was the 8-wave
+// shape; d_head 64 now runs two 4-wave workgroups per CU, see BW_THREADS.) ----
 // GT: grad_y and y arrive as [batch, E, S] (the transposed forward output and its gradient)
 template <typename T, bool GT>
-__global__ __launch_bounds__(MA_THREADS)
+__global__ __launch_bounds__(BW_THREADS)
 __attribute__((amdgpu_waves_per_eu(MA_ROWS_WAVES_PER_EU, MA_ROWS_WAVES_PER_EU)))
 void attention_mfma_backward_rows_kernel(
     const unsigned long long *__restrict__ masks, const unsigned char *__restrict__ cells,
@@ -1156,17 +1213,16 @@ void attention_mfma_backward_rows_kernel(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, c32 = lane & 31;
-    const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = bid / blocks_per_batch;
+    const BwBlock blk = bw_block(blocks_per_batch, wave, true);
+    const int b = blk.b;
     const DenseView dv = dense_view(b, S, MA_E, heads);
     const int RT = (S + MA_WROWS - 1) / MA_WROWS;
     const ScoreMap sm(scale, clampv);
-    const int i0 = MA_WROWS * folded_row_tile(bid % blocks_per_batch, blocks_per_batch, wave);
+    const int i0 = MA_WROWS * blk.tile;
     const CellTiles ct(masks, cells, pool, sat, b, RT, i0 / MA_WROWS, i0 < S);
-    const int last_tile = folded_row_tile(bid % blocks_per_batch, blocks_per_batch, MA_WAVES - 1);
-    const int T_ = min(RT, last_tile + 1);
-    const TileStager<T> stager(k + dv.base, v + dv.base, dv.ld, S, tid);
-    TileRegs<T> nxt = stager.load(0);
+    const int T_ = min(RT, blk.last + 1);
+    const TileStager<T, BW_THREADS> stager(k + dv.base, v + dv.base, dv.ld, S, tid);
+    TileRegs<T, BW_THREADS> nxt = stager.load(0);
     uint4 mcur = ct.load(0, lane), mnxt;
     // own rows: dY (B operand of dP = V dY^T), delta = max(1e-9, dY . Y), Q (B operand of D)
     Frag gf[MA_KS], qf[MA_KS];
@@ -1214,7 +1270,7 @@ void attention_mfma_backward_rows_kernel(
             q2 += __shfl_xor(q2, 32, SPT_WAVE);
         }
     }
-    const ClampGuard cg(bounds, b, blocks_per_batch, 1, q2, sm, clampv);
+    const ClampGuard cg(bounds, b, forward_slots(S), 1, q2, sm, clampv);
     __syncthreads();
 
     f32x16 qacc[MR_QTILES];
@@ -1281,8 +1337,8 @@ void attention_mfma_backward_rows_kernel(
 // registers) and walks the row tiles at or below the diagonal; 32 rows of Q and dY stream
 // through LDS as images Q rows | dY rows | Q cols | dY cols, plus the rows' 1 / row_sum and
 // delta.  Tiles are computed as D[row, key], so the sums over rows take the accumulator tile
-// as the A operand.  Folded like the rows: waves 0-3 own key tiles 4g .. 4g+3 (many row
-// tiles), waves 4-7 their mirror images (few).
+// as the A operand.  Which key tiles a workgroup's waves own: bw_block (the 8-wave shape folds
+// them like the rows; the 4-wave shape takes 4 consecutive key tiles, heaviest blocks first).
 // images: Q rows | dY (rows image, or -- GT, the operand arriving as [E][S] -- a cols image:
 // whichever its source layout fills with 8-byte stores; the other orientation of each operand
 // comes from the transposing read) | the rows' scaled delta
@@ -1295,8 +1351,8 @@ struct KeysStager {
     const float *w_b, *wd_b;    // the rows' 1 / row_sum and (1 / row_sum) delta, from the row-owned kernel
     int ld, S, tid;
     struct Regs {
-        typename Elem<T>::raw4 qf[MA_RPT], gf[MA_RPT];
-        float4 rs[MA_RPT];
+        typename Elem<T>::raw4 qf[BW_RPT], gf[BW_RPT];
+        float4 rs[BW_RPT];
         float st_wd;
     };
     // unconditional, clamped loads (see TileStager::load); rows >= S are given weight 0 by
@@ -1307,15 +1363,15 @@ struct KeysStager {
         const int i0 = rt * MA_WROWS;
         const int e4 = (tid % MA_EQ) * 4;
 #pragma unroll
-        for (int u = 0; u < MA_RPT; u++) {
-            const int il = tid / MA_EQ + MA_RPP * u;
+        for (int u = 0; u < BW_RPT; u++) {
+            const int il = tid / MA_EQ + BW_RPP * u;
             const int row = min(i0 + il, S - 1);
             r.qf[u] = ld_raw4(q_b + (size_t)row * ld + e4);
             if (!GT) {
                 r.gf[u] = ld_raw4(gy_b + (size_t)row * MA_E + e4);
                 r.rs[u] = make_float4(w_b[row], 0.f, 0.f, 0.f);
             } else {        // [E][S]: four consecutive rows of one e (S % 4 == 0)
-                const int e = (tid >> 3) + (MA_THREADS / 8) * u;
+                const int e = (tid >> 3) + (BW_THREADS / 8) * u;
                 const int i4 = min(i0 + (tid & 7) * 4, S - 4);
                 r.gf[u] = ld_raw4(gy_b + (size_t)e * S + i4);
                 r.rs[u] = *reinterpret_cast<const float4 *>(w_b + i4);
@@ -1333,8 +1389,8 @@ struct KeysStager {
         const int e4 = (tid % MA_EQ) * 4;
         auto weight = [&](float w, int row) { return row < S ? w : 0.0f; };
 #pragma unroll
-        for (int u = 0; u < MA_RPT; u++) {
-            const int il = tid / MA_EQ + MA_RPP * u;
+        for (int u = 0; u < BW_RPT; u++) {
+            const int il = tid / MA_EQ + BW_RPP * u;
             put_rows4(buf + MK_QR, il, e4, r.qf[u]);
             const float4 g = Elem<T>::f4(r.gf[u]);
             if (!GT) {
@@ -1342,7 +1398,7 @@ struct KeysStager {
                 put_rows4(buf + MK_G, il, e4, make_float4(w * g.x, w * g.y, w * g.z, w * g.w));
             } else {
                 const int i4 = (tid & 7) * 4;
-                put_cols4(buf + MK_G, (tid >> 3) + (MA_THREADS / 8) * u, i4,
+                put_cols4(buf + MK_G, (tid >> 3) + (BW_THREADS / 8) * u, i4,
                           make_float4(weight(r.rs[u].x, i0 + i4) * g.x,
                                       weight(r.rs[u].y, i0 + i4 + 1) * g.y,
                                       weight(r.rs[u].z, i0 + i4 + 2) * g.z,
@@ -1360,7 +1416,7 @@ struct KeysStager {
 // MODE 1: grad_v alone, all 128 columns (needs P only: no V fragments, no dP, no delta);
 // MODE 2: grad_k alone, 64 columns per launch.
 template <typename T, bool GT, int MODE>
-__global__ __launch_bounds__(MA_THREADS)
+__global__ __launch_bounds__(BW_THREADS)
 __attribute__((amdgpu_waves_per_eu(MA_KEYS_WAVES_PER_EU, MA_KEYS_WAVES_PER_EU)))
 void attention_mfma_backward_keys_kernel(
     const unsigned long long *__restrict__ masks, const unsigned char *__restrict__ cells_t,
@@ -1375,9 +1431,9 @@ void attention_mfma_backward_keys_kernel(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, c32 = lane & 31;
-    const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = bid / blocks_per_batch, g = bid % blocks_per_batch;
-    const int kt = folded_row_tile(g, blocks_per_batch, wave);
+    const BwBlock blk = bw_block(blocks_per_batch, wave, false);
+    const int b = blk.b;
+    const int kt = blk.tile;
     const int j0 = kt * MA_KT;
     const DenseView dv = dense_view(b, S, MA_E, heads);
     const int RT = (S + MA_WROWS - 1) / MA_WROWS;
@@ -1410,7 +1466,7 @@ void attention_mfma_backward_keys_kernel(
     // both parts) is parked in a wave-private LDS block instead and read back once per iteration, an
     // LDS read among two dozen others, on lgkmcnt.
     constexpr bool STASH_V = WANT_K && MA_E == 64 && sizeof(T) == 4;
-    char *const vstash = smem + 2 * MK_IMG + MA_WAVES * MA_PARK + wave * 2048 + 16 * lane;
+    char *const vstash = smem + 2 * MK_IMG + BW_WAVES * MA_PARK + wave * 2048 + 16 * lane;
     if constexpr (STASH_V) {
         *reinterpret_cast<uint4 *>(vstash) = make_uint4(vf[MA_KS - 1].hi.x, vf[MA_KS - 1].hi.y,
                                                         vf[MA_KS - 1].hi.z, vf[MA_KS - 1].hi.w);
@@ -1420,7 +1476,7 @@ void attention_mfma_backward_keys_kernel(
     // the slice's row-tile masks live in registers (lane rt: mask of row tile rt), so that the
     // loop body has no load whose result it needs at once
     // (grad_v needs P alone, which is continuous in the score: no exact mask for MODE 1)
-    const ClampGuard cg(WANT_K ? bounds : nullptr, b, blocks_per_batch, 0, k2, sm, clampv);
+    const ClampGuard cg(WANT_K ? bounds : nullptr, b, forward_slots(S), 0, k2, sm, clampv);
     // (round 4: ONE register -- this wave's key tile needs two bits per row tile, lane rt holds bit 0:
     // tile (rt, kt) is live, bit 1: it is stored in byte form; the 64-bit masks were four registers
     // of a kernel that has none to spare)
@@ -1451,7 +1507,7 @@ void attention_mfma_backward_keys_kernel(
         return cell_b[(tri(rc) + min(kt, rc)) * cstride + (c32 >> 2)];
     };
 
-    const int rt0 = (MA_WAVES / 2) * g;                 // the first row tile any wave needs
+    const int rt0 = blk.first;                          // the first row tile any wave needs
     const KeysStager<T, GT> stager{q + dv.base, gy + (size_t)b * S * MA_E, delta + (size_t)b * S,
                                    delta + ((size_t)(gridDim.x / blocks_per_batch) + b) * S, dv.ld, S, tid};
     stager.store(img, stager.load(min(rt0, RT - 1)), rt0);
@@ -1549,18 +1605,21 @@ void attention_mfma_backward_keys_kernel(
         __syncthreads();
     }
     if (have) {
+        // (the lane id from rare_lane(): the epilogue's lane offsets, formed before the loop and
+        // kept across it, were the one value of the fp32 GT MODE 0 kernel that went to scratch)
+        const int elane = rare_lane();
         float *tile = reinterpret_cast<float *>(img) + wave * (32 * MA_TLD);
         if constexpr (WANT_K) {
             T *gk_b = grad_k + dv.base + (size_t)j0 * dv.ld + 32 * MK_KTILES * half;
 #pragma unroll
             for (int eh = 0; eh < MK_KTILES; eh++)
-                store_acc_half(kacc[eh], scale, tile, gk_b + 32 * eh, dv.ld, S - j0, lane);
+                store_acc_half(kacc[eh], scale, tile, gk_b + 32 * eh, dv.ld, S - j0, elane);
         }
         if constexpr (WANT_V) {
             T *gv_b = grad_v + dv.base + (size_t)j0 * dv.ld + (MODE == 1 ? 0 : 64 * half);
 #pragma unroll
             for (int eh = 0; eh < NVT; eh++)
-                store_acc_half(vacc[eh], 1.0f, tile, gv_b + 32 * eh, dv.ld, S - j0, lane);
+                store_acc_half(vacc[eh], 1.0f, tile, gv_b + 32 * eh, dv.ld, S - j0, elane);
         }
     }
 }
@@ -1879,10 +1938,10 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
                              const float *bounds, float *delta, T *grad_q, T *grad_k, T *grad_v,
                              int batch_size, int S, float scale, float clamp, int heads,
                              int transposed, hipStream_t s) {
-    const int bpb = (S + MA_ROWS - 1) / MA_ROWS;
-    const dim3 grid((unsigned)batch_size * bpb), block(MA_THREADS);
-    const size_t lds_r = 2 * MA_IMG + (size_t)MA_WAVES * MA_PARK,
-                 lds_k = 2 * MK_IMG + (size_t)MA_WAVES * (MA_PARK + 2048);
+    const int bpb = (S + BW_ROWS - 1) / BW_ROWS;
+    const dim3 grid((unsigned)batch_size * bpb), block(BW_THREADS);
+    const size_t lds_r = 2 * MA_IMG + (size_t)BW_WAVES * MA_PARK,
+                 lds_k = 2 * MK_IMG + (size_t)BW_WAVES * (MA_PARK + 2048);
     // 64 gradient columns per launch (the accumulators of 128 would not fit the registers
     // beside the operands' fragments): d_head 128 runs each kernel twice
 #define SPT_MB(GT)                                                                              \

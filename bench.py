@@ -1,11 +1,12 @@
 """bench.py -- the SPT fine-tune step on MI355X (BASELINE.json configs[2]).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5   # the headline step alone
+    python bench.py --gpus 1 --full                  # + every other record listed below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # no launcher: bench.py starts its N ranks itself
     python bench.py --config llama-7b   # BASELINE.json configs[4] (opt-1.3b: configs[3])
-    python bench.py --only --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU; it
 starts N child rank processes of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, as
@@ -21,6 +22,9 @@ AdamW -- on resident synthetic tokens.  Data parallel: every rank its own micro-
 (weak scaling), identical replicas, the all-reduce INSIDE the timed step.
 
 Rank 0 prints ONE JSON line: tokens/s over all ranks and peak HBM, plus
+  roofline     -- the dominant HIP kernel of the headline step (the split-bf16 grouped GEMM),
+                  HIP events around every 7th launch inside the timed steps
+and, with --full only (each takes runs of its own after the headline's; --no-* drops one):
   full / lora  -- the same model and step as a dense full fine-tune and as LoRA only, on the
                   same GPU (the >= 2x / <= 50 % claims; N = 1 only)
   graphed      -- the headline step captured as one HIP graph (SparseTuner.capture), N = 1 only
@@ -28,8 +32,6 @@ Rank 0 prints ONE JSON line: tokens/s over all ranks and peak HBM, plus
                   (fwd + bwd + AdamW on randn[16, 512, 1024]): sparse / full / lora, and the
                   sparse step as a HIP graph
   attention    -- BASELINE.json configs[1] (sparse MHA only, fwd + bwd), last round's headline
-  roofline     -- the dominant HIP kernel of the headline step (the split-bf16 grouped GEMM),
-                  HIP events around every 7th launch inside the timed steps
   cpu_baseline -- the dense PyTorch-CPU counterpart of the same model step on the host's cores
                   (+ the single-core C oracle of the attention chain), N = 1 only
 """
@@ -693,8 +695,8 @@ def launch_ranks(n):
     return rc
 
 
-def main():
-    global CPU_REHEARSAL
+def parse_args(argv=None):
+    """The command line, with the --no-* switches of every record this run leaves out set."""
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None, help='default 20 (bert-large) / 8')
@@ -704,13 +706,16 @@ def main():
                          'llama-7b = configs[4]')
     ap.add_argument('--batch', type=int, default=None, help='micro-batch per GPU (default: the config\'s)')
     ap.add_argument('--layers', type=int, default=None)
-    ap.add_argument('--no-baselines', action='store_true', help='skip full / lora')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline step, also measure the baselines, block, attention, '
+                         'HIP-graph and CPU records (without it: the headline step alone)')
+    ap.add_argument('--no-baselines', action='store_true', help='with --full: skip full / lora')
     ap.add_argument('--no-block', action='store_true')
     ap.add_argument('--no-attention', action='store_true')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='skip the HIP-graph records')
     ap.add_argument('--no-gemm-events', action='store_true')
-    ap.add_argument('--only', action='store_true', help='the headline step alone')
+    ap.add_argument('--only', action='store_true', help='the headline step alone, even with --full')
     ap.add_argument('--backend', default='nccl', help="process-group backend (nccl = RCCL)")
     ap.add_argument('--one-device', action='store_true',
                     help='rehearsal of the N > 1 path on a one-GPU box: every rank on cuda:0 '
@@ -724,15 +729,26 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the headline step returned in its last '
                          'step (loss, clip norm, updated trainable parameters) as DIR/<name>.npy')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps is not None and args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.config == 'tiny-rehearsal' and not args.rehearse_cpu:
+        ap.error('--config tiny-rehearsal is the launcher test\'s model: use it with --rehearse-cpu')
+    if not args.full or args.only or args.rehearse_cpu:
+        args.no_baselines = args.no_block = args.no_attention = args.no_cpu = args.no_graph = True
+    if args.config != 'bert-large':
+        # the block / attention / graph / CPU records describe the headline workload
+        # (tools/bench_block.py, tools/bench_long.py measure them at the other dimensions)
+        args.no_block = args.no_attention = args.no_cpu = args.no_graph = True
+    return args
 
+
+def main():
+    global CPU_REHEARSAL
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args.gpus))         # before anything touches a GPU
 
-    if args.config == 'tiny-rehearsal' and not args.rehearse_cpu:
-        ap.error('--config tiny-rehearsal is the launcher test\'s model: use it with --rehearse-cpu')
     cfg = set_config(args.config)
     headline = args.config == 'bert-large'
     if args.steps is None:
@@ -743,12 +759,6 @@ def main():
         args.batch = cfg['batch']
     if args.layers is None:
         args.layers = cfg['layers']
-    if args.only or args.rehearse_cpu:
-        args.no_baselines = args.no_block = args.no_attention = args.no_cpu = args.no_graph = True
-    if not headline:
-        # the block / attention / graph / CPU records describe the headline workload
-        # (tools/bench_block.py, tools/bench_long.py measure them at the other dimensions)
-        args.no_block = args.no_attention = args.no_cpu = args.no_graph = True
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))

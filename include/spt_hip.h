@@ -160,7 +160,7 @@ int spt_lookup_forward(const int32_t *query, const int32_t *key, int32_t *out,
  *
  * Two forms (ABI 38).  Patterns as dense as lookup's (nnz >= S * S / 16; d_head 64, 128 <= S <= 1024, at
  * least 160 workgroups of 512 keys) are computed as DENSE 32-row stripes of scores on the matrix
- * cores (split-bf16, <= 2^-16 relative error per product), from which the CSR's entries are picked
+ * cores (split-bf16, <= 2^-15 relative error per product), from which the CSR's entries are picked
  * (csrc/sddmm_tile.hip: 36 us against 51-56 at the configs[2] shape); everything else by the fp32
  * gather kernels (csrc/sddmm.hip).  spt_sddmm_form() tells which one a call would take
  * (1 = matrix cores, 0 = gather); the environment variable SPT_SDDMM_GATHER forces the gather form.
@@ -186,7 +186,7 @@ int spt_sddmm_forward(const int32_t *indptr, const int32_t *indices,
  * default.  With SPT_SPMM_MFMA=1 in the environment (read at every call), patterns as dense as lookup's
  * (nnz >= S * S / 16, mean row length <= 64, d_head 64 or 128, 64 <= S <= 2048) are multiplied as DENSE
  * 32 x 32 tiles on the matrix cores: a wave assembles the tile of its 32 rows in LDS from the CSR
- * entries (duplicates add) and contracts it with the bf16 image of x (split-bf16, <= 2^-16 relative
+ * entries (duplicates add) and contracts it with the bf16 image of x (split-bf16, <= 2^-15 relative
  * error per product; csrc/mfma_attention.hip: spmm_mfma_kernel).  Opt-in because it is SLOWER at the
  * benchmark shape (65.7 against 46.3 us, profiles/r04_ops_kernels.txt; the kernel's header says
  * where the time goes).  spt_spmm_form() tells which form a call would take (1 = matrix cores,
@@ -308,7 +308,7 @@ int spt_sparse_attention_backward_rows(const int32_t *indices, const float *grad
  * The same attention core on the matrix cores (mfma_attention.hip): the CSR rows select the
  * live cells of dense 32 x 32 score tiles computed with v_mfma_f32_32x32x16_bf16 on fp32
  * operands split into two bf16 halves (three MFMAs per product, fp32 accumulation, relative
- * error <= 2^-16 per product).  Nothing of size nnz is written: the backward recomputes the
+ * error <= 2^-15 per product).  Nothing of size nnz is written: the backward recomputes the
  * tiles from q, k, v and the [batch, S] row sums.
  *   y[i]       = sum_p exp(s_p) v[col_p] / max(1e-9, row_sum[i]),
  *   s_p        = clamp(scale * q[i].k[col_p]),  entries with col_p > i take no part
@@ -479,7 +479,8 @@ typedef struct SptGroupedGemm {
     const void *w_image;
     /* SPT_EPI_ACT with ReLU only (mandatory there): Euclidean norms of the rows of `a`
      * [rows of a] and of the vectors W_g(n, :) [n_groups, n] (upper bounds do).  A product of split
-     * operands is off by <= 2^-16 |a| |w|; a pre-activation within that of ZERO would get
+     * operands is off by <= 2^-15 (1 + 2^-7) |a| |w| at worst, ~2^-16 typically (DESIGN.md section 3;
+     * the window below is 1.5 x 2^-16 |a| |w|, a measured one); a pre-activation within that of ZERO would get
      * the wrong ReLU derivative -- an O(1) error in that token's gradients (measured: 6 of
      * 614 k elements of one FFN).  The epilogue finds those elements (4e-4 of them at
      * k = 1024) from the norms and recomputes each as a plain fp32 dot product, read from
@@ -535,7 +536,7 @@ int spt_grouped_gemm_image_path(const SptGroupedGemm *desc);
  * bucket sizes are never read on the host).  Every element of out the groups address, and every
  * element of dbias, is written, zeros for a group without rows: no memset needed.
  * Arithmetic as spt_grouped_gemm: split-bf16 operands, three v_mfma_f32_32x32x16_bf16 per product,
- * fp32 accumulation, <= 2^-16 relative error per product.  The rows of every group are cut into
+ * fp32 accumulation, <= 2^-15 (1 + 2^-7) relative error per product.  The rows of every group are cut into
  * chunks of a size that depends on n_rows alone; each chunk's product goes to `workspace`, and a
  * second launch adds a group's chunks in chunk order: two calls give bitwise-equal results, no
  * inter-workgroup flags or atomics, no allocation, safe under graph capture.
@@ -597,7 +598,7 @@ int spt_grouped_gemm_bf16(const SptGroupedGemmBf16 *desc, void *stream);
  * side product of the routed LoRA FFN on bf16 storage, added after rowscale and bias:
  *     v[p, n] += sum_{j < r} a2[src2(p), j] * b2[g * b2_group_stride + n * b2_ldn + j]
  * a2 fp32 [*, lda2] (src2 = gather2 ? gather2[p] : p), b2 bf16; b2_group_stride 0 = one table for every
- * group.  a2 is split hi + lo (RNE bf16 parts) and each part multiplied exactly by b2: <= 2^-16 relative
+ * group.  a2 is split hi + lo (RNE bf16 parts) and each part multiplied exactly by b2: <= 2^-17 relative
  * per product, fp32 accumulation.  Every epilogue of spt_grouped_gemm_bf16 and `accumulate`; both weight
  * orientations (b2 stays k-contiguous).  Requires r % 4 == 0 and r <= 32 (SPT_EUNSUP), lda2 % 4 == 0,
  * b2_ldn % 4 == 0, b2_group_stride % 4 == 0, a2 16-byte and b2 8-byte aligned (SPT_ESHAPE); the main
@@ -615,7 +616,7 @@ int spt_grouped_gemm_bf16_ext(const SptGroupedGemmBf16 *desc, const SptGroupedGe
 /* spt_grouped_gemm_wgrad on bf16 G, A, out and dbias: same arguments, rules, chunking and in-order
  * reduction (fp32 chunk partials; bitwise reproducible, no atomics, capturable); out and dbias rounded
  * once.  Alignment: G, A, out and dbias 8-byte aligned (four bf16 per access), workspace 16-byte.  Products are exact without a rowscale; with one, rowscale * G is formed in fp32 and split
- * (<= 2^-16 relative per product).  The workspace is spt_grouped_gemm_wgrad_bf16_workspace_bytes. */
+ * (<= 2^-17 relative per product: only rowscale * G is split).  The workspace is spt_grouped_gemm_wgrad_bf16_workspace_bytes. */
 long long spt_grouped_gemm_wgrad_bf16_workspace_bytes(long long n_rows, int n_groups, int n, int k);
 int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const int32_t *gather_g,
                                 const void *a, long long lda, const int32_t *gather_a,
@@ -629,7 +630,7 @@ int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const int32_t *gat
  * lo = bf16(x - hi), laid out [row][ceil(cols / 32)][hi: 32 x bf16 | lo: 32 x bf16], i.e. one
  * 128-byte block per row and 32 columns (columns past `cols` in the last block are zero).
  * x = hi + lo to 2^-17 relative; three bf16 MFMAs (lo.hi + hi.lo + hi.hi) then give an fp32
- * product to 2^-16.  spt_split_bf16_bytes = rows * ceil(cols / 32) * 128.
+ * product to 2^-15 (1 + 2^-7) at worst.  spt_split_bf16_bytes = rows * ceil(cols / 32) * 128.
  * No reference counterpart: the reference multiplies in fp32 on cuBLAS (lora_ffn.py:87-111).
  */
 size_t spt_split_bf16_bytes(long long rows, int cols);
@@ -647,7 +648,7 @@ int spt_split_bf16(const float *src, void *image, long long rows, int cols, long
  *                  spt_split_bf16_bytes(rows, k) bytes) and `norms` [rows] (row 2-norms) -- NULL
  *                  to skip.  k % 32 == 0, n in {16, 32, 48, 64}: SPT_EUNSUP otherwise (callers
  *                  then use a library GEMM).
- * exact == 0: split-bf16 matrix-core products as in spt_grouped_gemm, <= 2^-16 relative per
+ * exact == 0: split-bf16 matrix-core products as in spt_grouped_gemm, <= 2^-15 relative per
  * product.  exact != 0: u in exact fp32 (the fp32-input MFMA, an fp32 FMA chain per element):
  * for the u that feeds the GEMM in front of a ReLU (lora_ffn.py:99-101), where a 2^-16 error
  * would decide the sign of pre-activations next to zero; 2-3 x the time at 48-64 columns.

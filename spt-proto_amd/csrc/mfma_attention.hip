@@ -791,8 +791,9 @@ struct ScoreMap {
 // `v = clamp(scale * sddmm, -10, 10)` (attention.py:125-127) passes gradient only inside the clamp.
 // That mask is a discontinuous function of the score, and a score formed from split-bf16 operands
 // carries an error of up to
-//     (3 * 2^-18 [the lo * lo term and the rounding of the lo parts] + 3 E * 2^-24 [fp32 accumulation
-//     of the 3 E products, worst case]) * sum_e |q_e k_e|  <=  MA_SPLIT_ERR * |q| |k|
+//     (2^-15 (1 + 2^-7) [the lo * lo term, <= 2^-16, and the rounding of the two lo parts, <= 2^-17 each:
+//     DESIGN.md section 3; 1.98 x 2^-16 measured on operands next to bf16 midpoints] + 3 E * 2^-24 [fp32
+//     accumulation of the 3 E products, worst case]) * sum_e |q_e k_e|  <=  MA_SPLIT_ERR * |q| |k|
 // so a cell that close to +-clamp can land on the other side of it than the reference's fp32 score
 // (measured before this: 7e-3 of grad_q on a layer with 15 % of its scores on the clamp).  The
 // backward kernels therefore recompute such cells -- |d| within eps of the bound, eps from the norm of
@@ -806,7 +807,7 @@ struct ScoreMap {
 // a ballot per tile; the recomputation
 // sits behind a wave-uniform branch (about 1e-4 of the live cells of a layer with scores of
 // standard deviation 10, none at all while the scores are O(1)).
-constexpr float MA_SPLIT_ERR = (1.0f + 3.0f * MA_E / 256.0f) * 1.52587890625e-5f;
+constexpr float MA_SPLIT_ERR = (2.015625f + 3.0f * MA_E / 256.0f) * 1.52587890625e-5f;
 // bounds [batch][MA_BOUND_SLOTS][2] floats, written by the forward's workgroup g of a slice:
 // [0] max over its rows of |q_i|^2, [1] an upper bound of max |k_j|^2 over the keys it staged
 constexpr int MA_BOUND_SLOTS = 8;                   // workgroups per slice: S <= 2048

@@ -313,7 +313,8 @@ int spt_sparse_attention_backward_rows(const int32_t *indices, const float *grad
  *   y[i]       = sum_p exp(s_p) v[col_p] / max(1e-9, row_sum[i]),
  *   s_p        = clamp(scale * q[i].k[col_p]),  entries with col_p > i take no part
  *   row_sum[i] = sum_p exp(s_p)                 (softmax.cu:17-30)
- * Any uniform-row CSR with Z = nnz / S <= 256, Z % 4 == 0, d_head 64 or 128, S <= 2048;
+ * Any uniform-row CSR with Z = nnz / S <= 256, Z % 4 == 0, d_head 64, 80 or 128, S <= 2048
+ * (d_head 80, OPT-2.7B's heads: same entries and ABI, dispatched to a third build of the kernels);
  * repeated columns count with their exact multiplicity (a row that holds ONE column Z = 256
  * times -- row 0 of a lookup pattern -- is kept as a byte count of 255 plus a per-row flag in
  * `tiles`; ABI 39: its row_sum is exact, no longer 255 / 256 of it).  SPT_EUNSUP otherwise.

@@ -29,18 +29,23 @@
 #include "spt_common.h"
 #include <stdlib.h>
 
-// The file is compiled twice: for d_head 64 (this is the unit that also holds the cell-tile
-// pass and the C entry points) and, with -DMA_E_VALUE=128, for d_head 128 into namespace
-// spt::e128 (mfma_attention_e128.o), to which the entry points dispatch.
+// The file is compiled three times: for d_head 64 (this is the unit that also holds the cell-tile
+// pass and the C entry points) and, with -DMA_E_VALUE=128 / 80, for d_head 128 / 80 into namespace
+// spt::e128 / spt::e80 (mfma_attention_e128.o / _e80.o), to which the entry points dispatch.
 #ifndef MA_E_VALUE
 #define MA_E_VALUE 64
 #endif
 #if MA_E_VALUE == 64
 #define MA_NS_OPEN namespace spt {
 #define MA_NS_CLOSE }
-#else
+#elif MA_E_VALUE == 128
 #define MA_NS_OPEN namespace spt { namespace e128 {
 #define MA_NS_CLOSE } }
+#elif MA_E_VALUE == 80
+#define MA_NS_OPEN namespace spt { namespace e80 {
+#define MA_NS_CLOSE } }
+#else
+#error "MA_E_VALUE: 64, 80 or 128"
 #endif
 
 MA_NS_OPEN
@@ -54,11 +59,15 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 #endif
 constexpr int MA_THREADS = MA_THREADS_VALUE;       // 512 or 256
 constexpr int MA_WAVES = MA_THREADS / SPT_WAVE;    // 8 or 4
-constexpr int MA_E = MA_E_VALUE;                   // d_head: 64 or 128
+constexpr int MA_E = MA_E_VALUE;                   // d_head: 64, 80 or 128
 constexpr int MA_EQ = MA_E / 4;                    // float4 per row of a tile
-constexpr int MA_KS = MA_E / 16;                   // k-steps of a contraction over e
-constexpr int MA_ET = MA_E / 32;                   // 32-column tiles of an [*, E] result
-constexpr int MA_BH = MA_E / 64;                   // backward launches: 64 gradient columns each
+constexpr int MA_KS = MA_E / 16;                   // k-steps of a contraction over e (80: 5, exact)
+// 32-column tiles of an [*, E] result.  d_head 80 takes a third tile whose last 16 columns are
+// never stored: its B-operand reads repeat columns 64 .. 79 there (read_cols_tr, read_cols), so
+// the padding lives in accumulator registers only -- no LDS image and no global access is wider
+// than E.  (+20 % on the products that produce E columns)
+constexpr int MA_ET = (MA_E + 31) / 32;
+constexpr int MA_ELAST = MA_E - 32 * (MA_ET - 1);  // stored columns of the last tile: 32 or 16
 constexpr int MA_WROWS = 32;                       // rows per wave = one MFMA tile
 constexpr int MA_ROWS = MA_WAVES * MA_WROWS;       // 256 rows per workgroup (the forward)
 constexpr int MA_KT = 32;                          // keys per tile
@@ -196,11 +205,17 @@ __device__ __forceinline__ void put_cols4(char *img, int e, int r4, const float4
 
 // Key tiles of the forward and of the row-owned backward: K rows image | V rows image (each
 // hi, lo).  With NT threads staging, thread t stages the four elements (row t / (E/4) + RPP u,
-// columns 4 (t % (E/4)) ..) for u < RPT.
+// columns 4 (t % (E/4)) ..) for u < RPT.  d_head 80 (EVEN false: 640 float4s per tile, 20 per
+// row) numbers the tile's float4s f = t + NT u instead, row f / 20, columns 4 (f % 20) ..; the
+// last round is partial: its loads are clamped to float4 F - 1, its stores skipped.
 template <int NT>
 struct Share {
-    static constexpr int RPT = 32 * MA_EQ / NT;      // 32 x E tile: float4s per thread to stage
-    static constexpr int RPP = NT / MA_EQ;           // tile rows covered by one float4 per thread
+    static constexpr int F = 32 * MA_EQ;             // float4s of a 32 x E tile
+    static constexpr bool EVEN = F % NT == 0 && NT % MA_EQ == 0;
+    static constexpr int RPT = (F + NT - 1) / NT;    // 32 x E tile: float4s per thread to stage
+    static constexpr int RPP = NT / MA_EQ;           // tile rows covered by one float4 per thread (EVEN)
+    static __device__ __forceinline__ int slot(int t, int u) { return min(t + NT * u, F - 1); }
+    static __device__ __forceinline__ bool owns(int t, int u) { return F % NT == 0 || t + NT * u < F; }
 };
 template <typename T, int NT = MA_THREADS>
 struct TileRegs { typename Elem<T>::raw4 kf[Share<NT>::RPT], vf[Share<NT>::RPT]; };
@@ -208,9 +223,9 @@ template <typename T, int NT = MA_THREADS>
 struct TileStager {
     static constexpr int RPT = Share<NT>::RPT, RPP = Share<NT>::RPP;
     const T *k_b, *v_b;
-    int ld, S, jl, e4;
-    __device__ __forceinline__ TileStager(const T *k, const T *v, int ld_, int S_, int tid)
-        : k_b(k), v_b(v), ld(ld_), S(S_), jl(tid / MA_EQ), e4((tid % MA_EQ) * 4) {}
+    int ld, S, jl, e4, tid;
+    __device__ __forceinline__ TileStager(const T *k, const T *v, int ld_, int S_, int tid_)
+        : k_b(k), v_b(v), ld(ld_), S(S_), jl(tid_ / MA_EQ), e4((tid_ % MA_EQ) * 4), tid(tid_) {}
     // Unconditional loads with clamped rows: a load under a branch makes the compiler wait
     // with vmcnt(0) for OLDER loads too (it cannot count what the branch issued), which
     // exposed the full memory latency in every iteration.  Keys >= S read row S - 1: finite
@@ -219,20 +234,34 @@ struct TileStager {
         TileRegs<T, NT> r;
 #pragma unroll
         for (int u = 0; u < RPT; u++) {
-            const int j = min(t * MA_KT + jl + RPP * u, S - 1);
-            r.kf[u] = ld_raw4(k_b + (size_t)j * ld + e4);
-            r.vf[u] = ld_raw4(v_b + (size_t)j * ld + e4);
+            if constexpr (Share<NT>::EVEN) {
+                const int j = min(t * MA_KT + jl + RPP * u, S - 1);
+                r.kf[u] = ld_raw4(k_b + (size_t)j * ld + e4);
+                r.vf[u] = ld_raw4(v_b + (size_t)j * ld + e4);
+            } else {
+                const int f = Share<NT>::slot(tid, u);
+                const int j = min(t * MA_KT + f / MA_EQ, S - 1), c4 = (f % MA_EQ) * 4;
+                r.kf[u] = ld_raw4(k_b + (size_t)j * ld + c4);
+                r.vf[u] = ld_raw4(v_b + (size_t)j * ld + c4);
+            }
         }
         return r;
     }
     __device__ __forceinline__ void store(char *buf, const TileRegs<T, NT> &r) const {
 #pragma unroll
         for (int u = 0; u < RPT; u++) {
-            put_rows4(buf + MA_KH, jl + RPP * u, e4, r.kf[u]);
-            put_rows4(buf + MA_VH, jl + RPP * u, e4, r.vf[u]);
+            if constexpr (Share<NT>::EVEN) {
+                put_rows4(buf + MA_KH, jl + RPP * u, e4, r.kf[u]);
+                put_rows4(buf + MA_VH, jl + RPP * u, e4, r.vf[u]);
+            } else if (Share<NT>::owns(tid, u)) {
+                const int f = tid + NT * u;
+                put_rows4(buf + MA_KH, f / MA_EQ, (f % MA_EQ) * 4, r.kf[u]);
+                put_rows4(buf + MA_VH, f / MA_EQ, (f % MA_EQ) * 4, r.vf[u]);
+            }
         }
     }
-    // max over this thread's K rows of the tile of the sum of squares of its four columns
+    // max over this thread's K rows of the tile of the sum of squares of its four columns (not
+    // EVEN: of its float4s, whichever columns they hold)
     __device__ __forceinline__ float k_share(const TileRegs<T, NT> &r) const {
         float best = 0.f;
 #pragma unroll
@@ -257,7 +286,10 @@ __device__ __forceinline__ Frag read_rows(const char *hi, const char *lo, int la
 // B-operand fragment whose k order matches an accumulator tile used as the A operand
 // (k-step s, element jj of lane half h <-> tile row 16s + 8(jj>>2) + 4h + (jj&3)):
 // lane (c, h) reads row c of the transposed image at 16s + 4h .. +4 and 16s + 8 + 4h .. +4
+// (rows >= E -- the last tile's unstored columns at d_head 80 -- read row row - 16 instead)
 __device__ __forceinline__ Frag read_cols(const char *hi, const char *lo, int row, int h, int s) {
+    if constexpr (MA_E % 32 != 0)
+        if (row >= MA_E) row -= 16;
     const int off = row * MA_VLD + 32 * s + 8 * h;
 
     const uint2 a = *reinterpret_cast<const uint2 *>(hi + off),
@@ -276,7 +308,9 @@ __device__ __forceinline__ Frag read_cols(const char *hi, const char *lo, int ro
 // row q, columns 4p .. 4p + 3.  Two blocks (tile rows 16s + 4h .. and 16s + 8 + 4h ..) give
 // elements 0..3 and 4..7; the group's columns are 16 (lane >> 4 & 1) .. + 15 of the 32-column
 // half `col0`.  No transposed copy of the tile and none of its 2-byte scattered stores.
-// (All 64 lanes must be active: the gather crosses lanes.)
+// (All 64 lanes must be active: the gather crosses lanes.)  A half whose upper 16 columns lie
+// beyond E (d_head 80, col0 = 64) reads its lower 16 columns twice: output columns 80 .. 95 of
+// the product are then copies of 64 .. 79 and are never stored.
 typedef short v4s16 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 lds_tr_b64(const char *p) {
     const v4s16 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
@@ -287,7 +321,9 @@ template <int NP>
 __device__ __forceinline__ Frag read_cols_tr(const char *hi, const char *lo, int col0, int lane,
                                              int s) {
     const int gl = lane & 15, q = gl >> 2, p = gl & 3, h = lane >> 5;
-    const int off = (16 * s + 4 * h + q) * MA_KLD + (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
+    int off = (16 * s + 4 * h + q) * MA_KLD + (col0 + 16 * ((lane >> 4) & 1) + 4 * p) * 2;
+    if constexpr (MA_E % 32 != 0)
+        if (col0 + 16 >= MA_E) off = (16 * s + 4 * h + q) * MA_KLD + (col0 + 4 * p) * 2;
     const uint2 a = lds_tr_b64(hi + off), b = lds_tr_b64(hi + off + 8 * MA_KLD);
     Frag f;
     f.hi = make_uint4(a.x, a.y, b.x, b.y);
@@ -345,10 +381,12 @@ __device__ __forceinline__ void split_own_rows(Frag (&f)[MA_KS], const float (&x
 // LDS tile of 32 x MA_TLD floats, one 32-column half at a time.
 //
 // One e-half of a wave's 32-row accumulator tile (column = lane & 31, rows in the registers)
-// -> rows of `dst` (row stride ld elements), 8 rows x 32 elements per store instruction.
+// -> rows of `dst` (row stride ld elements), 8 rows x 32 elements per store instruction; only
+// its first `cols` columns (32, or 16 for the last tile at d_head 80).
 template <typename T>
 __device__ __forceinline__ void store_acc_half(const f32x16 &acc, float mult, float *tile,
-                                               T *dst, size_t ld, int rows_left, int lane) {
+                                               T *dst, size_t ld, int rows_left, int lane,
+                                               int cols = 32) {
     const int c32 = lane & 31, h = lane >> 5;
 #pragma unroll
     for (int r = 0; r < 16; r++) tile[acc_row(r, h) * MA_TLD + c32] = acc[r] * mult;
@@ -357,7 +395,7 @@ __device__ __forceinline__ void store_acc_half(const f32x16 &acc, float mult, fl
     for (int k = 0; k < 4; k++) {
         const int row = (lane >> 3) + 8 * k, e4 = (lane & 7) * 4;
         const float4 o = *reinterpret_cast<const float4 *>(tile + row * MA_TLD + e4);
-        if (row < rows_left) st4(dst + (size_t)row * ld + e4, o);
+        if (row < rows_left && (MA_E % 32 == 0 || e4 < cols)) st4(dst + (size_t)row * ld + e4, o);
     }
     wave_lds_fence();
 }
@@ -370,15 +408,16 @@ __device__ __forceinline__ void load_own_rows_transposed(float (&x)[MA_E / 2], c
     const int i4 = min(i0 + (lane & 7) * 4, S - 4) - i0;      // (S % 4 == 0; rows >= S unused)
 #pragma unroll
     for (int hf = 0; hf < MA_ET; hf++) {
+        const int ne = hf + 1 < MA_ET ? 32 : MA_ELAST;        // e of this 32-e group (80: 32, 32, 16)
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < ne / 8; k++) {
             const int el = (lane >> 3) + 8 * k;
             const float4 v4 = ld4(src + (size_t)(32 * hf + el) * S + i0 + i4);
             *reinterpret_cast<float4 *>(tile + el * MA_TLD + (lane & 7) * 4) = v4;
         }
         wave_lds_fence();
 #pragma unroll
-        for (int kk = 0; kk < 2; kk++) {
+        for (int kk = 0; kk < ne / 16; kk++) {
 #pragma unroll
             for (int j = 0; j < 8; j++)
                 x[8 * (2 * hf + kk) + j] = tile[(8 * h + 16 * kk + j) * MA_TLD + c32];
@@ -936,6 +975,9 @@ __device__ __forceinline__ void clamp_exact(f32x16 &d, f32x16 &dp, char *park0, 
 // their VALU phases coincide).
 constexpr int MK_KTILES = MA_ET;    // 32-column tiles of grad_k per launch of the key-owned kernel
 constexpr int MR_QTILES = MA_ET;    // 32-column tiles of grad_q per launch of the row-owned kernel
+// grad_k and grad_v in ONE key-owned launch (MODE 0) only at d_head 64; past it the K and V
+// fragments and both sets of accumulators do not fit 256 registers (MODE 1 + MODE 2)
+constexpr bool MK_FUSED = MA_E <= 64;
 #define MA_ROWS_WAVES_PER_EU 2
 #define MA_KEYS_WAVES_PER_EU 2
 template <typename T, bool YT>
@@ -1044,10 +1086,19 @@ void attention_mfma_forward_kernel(
     if (bounds) {                                       // (kernel argument: uniform)
         // columns: lanes with equal tid % MA_EQ; rows: the other lane bits
         float km = k2part;
+        if constexpr (Share<MA_THREADS>::EVEN) {
 #pragma unroll
-        for (int off = MA_EQ; off < SPT_WAVE; off <<= 1) km = fmaxf(km, __shfl_xor(km, off, SPT_WAVE));
+            for (int off = MA_EQ; off < SPT_WAVE; off <<= 1) km = fmaxf(km, __shfl_xor(km, off, SPT_WAVE));
 #pragma unroll
-        for (int off = 1; off < MA_EQ; off <<= 1) km += __shfl_xor(km, off, SPT_WAVE);
+            for (int off = 1; off < MA_EQ; off <<= 1) km += __shfl_xor(km, off, SPT_WAVE);
+        } else {
+            // a thread's float4s hold varying columns: |k_j|^2, a sum of MA_EQ four-column
+            // shares, is at most MA_EQ times the largest share any thread staged (the maximum
+            // over the waves is taken below)
+#pragma unroll
+            for (int off = 1; off < SPT_WAVE; off <<= 1) km = fmaxf(km, __shfl_xor(km, off, SPT_WAVE));
+            km *= (float)MA_EQ;
+        }
         float qm = q2 + __shfl_xor(q2, 32, SPT_WAVE);   // the two lane halves hold half a row each
 #pragma unroll
         for (int off = 1; off < 32; off <<= 1) qm = fmaxf(qm, __shfl_xor(qm, off, SPT_WAVE));
@@ -1084,7 +1135,8 @@ void attention_mfma_forward_kernel(
                 if (i0 + il < S) {
 #pragma unroll
                     for (int eh = 0; eh < MA_ET; eh++)
-                        st1(y_b + (size_t)(i0 + il) * MA_E + 32 * eh + c32, yacc[eh][r] * sc);
+                        if (MA_E % 32 == 0 || 32 * eh + c32 < MA_E)
+                            st1(y_b + (size_t)(i0 + il) * MA_E + 32 * eh + c32, yacc[eh][r] * sc);
                 }
             }
         } else {
@@ -1105,7 +1157,7 @@ void attention_mfma_forward_kernel(
                 }
                 wave_lds_fence();
 #pragma unroll
-                for (int k4 = 0; k4 < 4; k4++) {
+                for (int k4 = 0; k4 < (eh + 1 < MA_ET ? 32 : MA_ELAST) / 8; k4++) {
                     const int el = (lane >> 3) + 8 * k4, i4 = (lane & 7) * 4;
                     const float4 o = *reinterpret_cast<const float4 *>(tile + el * MA_TLD + i4);
                     T *dst = y_b + (size_t)(el + 32 * eh) * S + i0 + i4;
@@ -1330,7 +1382,8 @@ void attention_mfma_backward_rows_kernel(
         T *gq_b = grad_q + dv.base + (size_t)i0 * dv.ld + 32 * MR_QTILES * half;
 #pragma unroll
         for (int eh = 0; eh < MR_QTILES; eh++)
-            store_acc_half(qacc[eh], 1.0f, tile, gq_b + 32 * eh, dv.ld, S - i0, lane);
+            store_acc_half(qacc[eh], 1.0f, tile, gq_b + 32 * eh, dv.ld, S - i0, lane,
+                           eh + 1 < MR_QTILES ? 32 : MA_ELAST);
     }
 }
 
@@ -1356,6 +1409,10 @@ struct KeysStager {
         float4 rs[BW_RPT];
         float st_wd;
     };
+    // (not Share::EVEN -- d_head 80 -- float4 u of thread t is slot f = t + BW_THREADS u: tile
+    // row f / MA_EQ, columns 4 (f % MA_EQ) .., or (GT) e = f / 8; loads clamped, stores skipped
+    // past the tile, as in TileStager)
+    static constexpr bool EVEN = Share<BW_THREADS>::EVEN;
     // unconditional, clamped loads (see TileStager::load); rows >= S are given weight 0 by
     // store(), so whatever finite data the clamped rows hold never counts.  Raw values only:
     // arithmetic on them here would wait for the loads at the top of the iteration.
@@ -1365,14 +1422,20 @@ struct KeysStager {
         const int e4 = (tid % MA_EQ) * 4;
 #pragma unroll
         for (int u = 0; u < BW_RPT; u++) {
-            const int il = tid / MA_EQ + BW_RPP * u;
+            int il = tid / MA_EQ + BW_RPP * u, c4 = e4;
+            if constexpr (!EVEN) {
+                const int f = Share<BW_THREADS>::slot(tid, u);
+                il = f / MA_EQ;
+                c4 = (f % MA_EQ) * 4;
+            }
             const int row = min(i0 + il, S - 1);
-            r.qf[u] = ld_raw4(q_b + (size_t)row * ld + e4);
+            r.qf[u] = ld_raw4(q_b + (size_t)row * ld + c4);
             if (!GT) {
-                r.gf[u] = ld_raw4(gy_b + (size_t)row * MA_E + e4);
+                r.gf[u] = ld_raw4(gy_b + (size_t)row * MA_E + c4);
                 r.rs[u] = make_float4(w_b[row], 0.f, 0.f, 0.f);
             } else {        // [E][S]: four consecutive rows of one e (S % 4 == 0)
-                const int e = (tid >> 3) + (BW_THREADS / 8) * u;
+                int e = (tid >> 3) + (BW_THREADS / 8) * u;
+                if constexpr (!EVEN) e = Share<BW_THREADS>::slot(tid, u) >> 3;
                 const int i4 = min(i0 + (tid & 7) * 4, S - 4);
                 r.gf[u] = ld_raw4(gy_b + (size_t)e * S + i4);
                 r.rs[u] = *reinterpret_cast<const float4 *>(w_b + i4);
@@ -1391,12 +1454,17 @@ struct KeysStager {
         auto weight = [&](float w, int row) { return row < S ? w : 0.0f; };
 #pragma unroll
         for (int u = 0; u < BW_RPT; u++) {
-            const int il = tid / MA_EQ + BW_RPP * u;
-            put_rows4(buf + MK_QR, il, e4, r.qf[u]);
+            int il = tid / MA_EQ + BW_RPP * u, c4 = e4;
+            if constexpr (!EVEN) {
+                if (!Share<BW_THREADS>::owns(tid, u)) continue;
+                il = (tid + BW_THREADS * u) / MA_EQ;
+                c4 = ((tid + BW_THREADS * u) % MA_EQ) * 4;
+            }
+            put_rows4(buf + MK_QR, il, c4, r.qf[u]);
             const float4 g = Elem<T>::f4(r.gf[u]);
             if (!GT) {
                 const float w = weight(r.rs[u].x, i0 + il);
-                put_rows4(buf + MK_G, il, e4, make_float4(w * g.x, w * g.y, w * g.z, w * g.w));
+                put_rows4(buf + MK_G, il, c4, make_float4(w * g.x, w * g.y, w * g.z, w * g.w));
             } else {
                 const int i4 = (tid & 7) * 4;
                 put_cols4(buf + MK_G, (tid >> 3) + (BW_THREADS / 8) * u, i4,
@@ -1414,8 +1482,9 @@ struct KeysStager {
 // MODE 0: grad_k and grad_v together, 64 columns (`half`) per launch -- d_head 64.
 // d_head 128 cannot hold K, V fragments (128 registers) and four accumulator tiles beside the
 // tile arithmetic (the combined kernel spilled 41-60 registers: 281 us per launch), so there
-// MODE 1: grad_v alone, all 128 columns (needs P only: no V fragments, no dP, no delta);
-// MODE 2: grad_k alone, 64 columns per launch.
+// MODE 1: grad_v alone, all E columns (needs P only: no V fragments, no dP, no delta);
+// MODE 2: grad_k alone, all E columns.  d_head 80 takes the same split (K, V: 80 registers, six
+// accumulator tiles: 96) -- see MK_FUSED.
 template <typename T, bool GT, int MODE>
 __global__ __launch_bounds__(BW_THREADS)
 __attribute__((amdgpu_waves_per_eu(MA_KEYS_WAVES_PER_EU, MA_KEYS_WAVES_PER_EU)))
@@ -1614,13 +1683,15 @@ void attention_mfma_backward_keys_kernel(
             T *gk_b = grad_k + dv.base + (size_t)j0 * dv.ld + 32 * MK_KTILES * half;
 #pragma unroll
             for (int eh = 0; eh < MK_KTILES; eh++)
-                store_acc_half(kacc[eh], scale, tile, gk_b + 32 * eh, dv.ld, S - j0, elane);
+                store_acc_half(kacc[eh], scale, tile, gk_b + 32 * eh, dv.ld, S - j0, elane,
+                               eh + 1 < MK_KTILES ? 32 : MA_ELAST);
         }
         if constexpr (WANT_V) {
             T *gv_b = grad_v + dv.base + (size_t)j0 * dv.ld + (MODE == 1 ? 0 : 64 * half);
 #pragma unroll
             for (int eh = 0; eh < NVT; eh++)
-                store_acc_half(vacc[eh], 1.0f, tile, gv_b + 32 * eh, dv.ld, S - j0, elane);
+                store_acc_half(vacc[eh], 1.0f, tile, gv_b + 32 * eh, dv.ld, S - j0, elane,
+                               eh + 1 < NVT ? 32 : MA_ELAST);
         }
     }
 }
@@ -1682,6 +1753,7 @@ static size_t mfma_forward_lds() {
 // workgroups per CU in ONE round, and the next row block's entries in flight during the tile loop --
 // both against the register budget; the fused forward (attention_mfma_forward_kernel) does the same
 // product in 44 us INCLUDING the scores and the softmax because its P tile never leaves registers.
+#if MA_E_VALUE % 32 == 0     // (the operator form covers d_head 64 and 128: spmm_mfma_takes)
 constexpr int SN_THREADS = 256;
 constexpr int SN_WAVES = SN_THREADS / SPT_WAVE;
 constexpr int SN_ROWS = SN_WAVES * MA_WROWS;
@@ -1908,8 +1980,9 @@ int launch_spmm_mfma(const int32_t *indptr, const int32_t *indices, const float 
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }
+#endif
 
-// ---- launchers of this head dimension (the d_head 64 unit dispatches to spt::e128's) ----
+// ---- launchers of this head dimension (the d_head 64 unit dispatches to spt::e80's, e128's) ----
 template <typename T>
 static int launch_forward_t(const unsigned long long *masks, const unsigned char *cells,
                             const unsigned char *pool, const unsigned *sat, const T *q, const T *k,
@@ -1954,7 +2027,7 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
             hipLaunchKernelGGL((attention_mfma_backward_rows_kernel<T, GT>), grid, block, lds_r, \
                                s, masks, cells, pool, sat, q, k, v, grad_y, y, row_sum, bounds, \
                                grad_q, delta, S, scale, clamp, heads, bpb, half);               \
-        if (MA_BH == 1) {                                                                       \
+        if constexpr (MK_FUSED) {                                                               \
             SPT_KEYS(GT, 0, 0);                                                                 \
         } else {                                                                                \
             SPT_KEYS(GT, 1, 0);                                                                 \
@@ -2028,6 +2101,20 @@ int launch_backward(const unsigned long long *masks, const unsigned char *cells,
                     void *grad_k, void *grad_v, int batch_size, int S, float scale, float clamp,
                     int heads, int transposed, hipStream_t s);
 }  // namespace e128
+namespace e80 {
+int launch_forward(const unsigned long long *masks, const unsigned char *cells,
+                   const unsigned char *pool, const unsigned *sat, int dtype, const void *q,
+                   const void *k, const void *v, void *y, float *row_sum, float *bounds,
+                   int batch_size, int S, float scale, float clamp, int heads, int y_transposed,
+                   hipStream_t s);
+int launch_backward(const unsigned long long *masks, const unsigned char *cells,
+                    const unsigned char *cells_t, const unsigned char *pool,
+                    const unsigned char *pool_t, const unsigned *sat, int dtype, const void *q,
+                    const void *k, const void *v, const void *y, const void *grad_y,
+                    const float *row_sum, const float *bounds, float *delta, void *grad_q,
+                    void *grad_k, void *grad_v, int batch_size, int S, float scale, float clamp,
+                    int heads, int transposed, hipStream_t s);
+}  // namespace e80
 
 namespace e128 {
 int launch_spmm_mfma(const int32_t *indptr, const int32_t *indices, const float *values, const float *x,
@@ -2053,7 +2140,7 @@ int spmm_mfma_launch(const int32_t *indptr, const int32_t *indices, const float 
 }
 
 static bool mfma_shape_ok(int S, int E, int nnz) {
-    if ((E != 64 && E != 128) || S <= 0 || nnz <= 0 || nnz % S != 0) return false;
+    if ((E != 64 && E != 80 && E != 128) || S <= 0 || nnz <= 0 || nnz % S != 0) return false;
     const int Z = nnz / S;
     return Z <= MA_MAXZ && Z % 4 == 0 && S <= MA_MAXNT * MA_KT;
 }
@@ -2164,12 +2251,9 @@ static int mfma_forward_any(const void *tiles, int layout, int dtype, const void
     if (heads > 0 && batch_size % heads != 0) return SPT_ESHAPE;
     const TileSet ts = carve_tiles(const_cast<void *>(tiles), batch_size, seq_length, layout);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return d_head == 64
-               ? launch_forward(ts.masks, ts.cells, ts.pool, ts.sat, dtype, q, k, v, y, row_sum, bounds,
-                                batch_size, seq_length, scale, clamp, heads, y_transposed, s)
-               : e128::launch_forward(ts.masks, ts.cells, ts.pool, ts.sat, dtype, q, k, v, y, row_sum,
-                                      bounds, batch_size, seq_length, scale, clamp, heads,
-                                      y_transposed, s);
+    auto fwd = d_head == 64 ? launch_forward : d_head == 80 ? e80::launch_forward : e128::launch_forward;
+    return fwd(ts.masks, ts.cells, ts.pool, ts.sat, dtype, q, k, v, y, row_sum, bounds, batch_size,
+               seq_length, scale, clamp, heads, y_transposed, s);
 }
 
 static int mfma_backward_any(const void *tiles, int layout, int dtype, const void *q,
@@ -2189,14 +2273,10 @@ static int mfma_backward_any(const void *tiles, int layout, int dtype, const voi
     if (transposed && (seq_length & 3)) return SPT_EUNSUP;
     const TileSet ts = carve_tiles(const_cast<void *>(tiles), batch_size, seq_length, layout);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return d_head == 64
-               ? launch_backward(ts.masks, ts.cells, ts.cells_t, ts.pool, ts.pool_t, ts.sat, dtype, q,
-                                 k, v, y, grad_y, row_sum, bounds, delta, grad_q, grad_k, grad_v,
-                                 batch_size, seq_length, scale, clamp, heads, transposed, s)
-               : e128::launch_backward(ts.masks, ts.cells, ts.cells_t, ts.pool, ts.pool_t, ts.sat,
-                                       dtype, q, k, v, y, grad_y, row_sum, bounds, delta, grad_q,
-                                       grad_k, grad_v, batch_size, seq_length, scale, clamp, heads,
-                                       transposed, s);
+    auto bwd = d_head == 64 ? launch_backward : d_head == 80 ? e80::launch_backward : e128::launch_backward;
+    return bwd(ts.masks, ts.cells, ts.cells_t, ts.pool, ts.pool_t, ts.sat, dtype, q, k, v, y, grad_y,
+               row_sum, bounds, delta, grad_q, grad_k, grad_v, batch_size, seq_length, scale, clamp,
+               heads, transposed, s);
 }
 
 extern "C" int spt_attention_mfma_forward(const void *tiles, int layout, const float *q,

@@ -448,16 +448,34 @@ __global__ __launch_bounds__(PQL_THREADS, NL == 4 ? 3 : 2) void pq_loss_backward
     }
 
     // lanes l, l + NL M, l + 2 NL M .. of a wave hold the same (subspace, part): butterfly over
-    // those, then the waves of the block through LDS
+    // those (M a power of two; else lane l < NL M adds the others in ascending order), then the
+    // waves of the block through LDS
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int step = NL * M; step < 64; step <<= 1) {
+    if ((M & (M - 1)) == 0) {
+        for (int step = NL * M; step < 64; step <<= 1) {
 #pragma unroll
-        for (int c = 0; c < CL; c++)
+            for (int c = 0; c < CL; c++)
 #pragma unroll
-            for (int p = 0; p < D / 2; p++) {
-                gt[c][p].x += __shfl_xor(gt[c][p].x, step, 64);
-                gt[c][p].y += __shfl_xor(gt[c][p].y, step, 64);
-            }
+                for (int p = 0; p < D / 2; p++) {
+                    gt[c][p].x += __shfl_xor(gt[c][p].x, step, 64);
+                    gt[c][p].y += __shfl_xor(gt[c][p].y, step, 64);
+                }
+        }
+    } else {
+        for (int from = NL * M; from < 64; from += NL * M) {
+            const int src = min(lane + from, 63);
+            const bool take = lane < NL * M && lane + from < 64;    // (the sources stay unmodified)
+#pragma unroll
+            for (int c = 0; c < CL; c++)
+#pragma unroll
+                for (int p = 0; p < D / 2; p++) {
+                    const float x = __shfl(gt[c][p].x, src, 64), y = __shfl(gt[c][p].y, src, 64);
+                    if (take) {
+                        gt[c][p].x += x;
+                        gt[c][p].y += y;
+                    }
+                }
+        }
     }
     if (lane < NL * M) {
         float *dst = red + ((size_t)wave * M + m) * CD + part * CL * D;
@@ -511,13 +529,21 @@ __global__ __launch_bounds__(1024) void pq_loss_table_reduce_kernel(
 
 static bool pq_loss_shape_ok(long long n_vectors, int M, int C, int D) {
     if (C != PQL_C || (D != 4 && D != 8)) return false;
-    if (M <= 0 || M > 32 || (M & (M - 1)) != 0) return false;
+    if (M <= 0 || M > 32) return false;          // (any M: 10 is OPT-2.7B's d_head 80 / 8)
     return n_vectors * M < 0x7FFFFFFFLL - 4 * 1024 * 1024;
 }
 
-static int pq_loss_blocks(long long total, int cap = 512) {
+static int gcd_int(int a, int b) { return b == 0 ? a : gcd_int(b, a % b); }
+// `total` lanes of work, `per_block` sub-vectors per block and grid-stride step.  A grid of fewer
+// than `cap` blocks covers every sub-vector in one step; a capped grid is rounded down to a
+// multiple of M / gcd(M, per_block), so that its stride nblk * per_block is a multiple of M and a
+// lane's subspace never changes (M a power of two <= 32: the cap itself, as before)
+static int pq_loss_blocks(long long total, int M, int per_block = PQL_THREADS, int cap = 512) {
     long long nblk = (total + PQL_THREADS - 1) / PQL_THREADS;
-    if (nblk > cap) nblk = cap;  // `cap / 256` blocks per CU; the grid stride cap * 256 / NL is a multiple of M
+    if (nblk > cap) {
+        const int unit = M / gcd_int(M, per_block);
+        nblk = cap - cap % unit;  // `cap / 256` blocks per CU
+    }
     return (int)nblk;
 }
 // lanes per sub-vector of the backward (pq_loss_backward_kernel): 2; SPT_PQ_LANES=4 runs the
@@ -532,9 +558,9 @@ static int pq_backward_lanes() {
     }
     return lanes;
 }
-static int pq_backward_blocks(long long total) {
+static int pq_backward_blocks(long long total, int M) {
     const int nl = pq_backward_lanes();
-    return pq_loss_blocks((long long)nl * total, nl == 4 ? 768 : 512);
+    return pq_loss_blocks((long long)nl * total, M, PQL_THREADS / nl, nl == 4 ? 768 : 512);
 }
 
 }  // namespace spt
@@ -544,7 +570,7 @@ using namespace spt;
 extern "C" int64_t spt_pq_loss_workspace_bytes(int64_t n_vectors, int n_subspaces,
                                                int n_codewords, int d_code) {
     if (n_vectors <= 0 || !pq_loss_shape_ok(n_vectors, n_subspaces, n_codewords, d_code)) return 0;
-    const int nblk = pq_loss_blocks(4 * n_vectors * n_subspaces, 1024);   // backward: upper bound
+    const int nblk = pq_loss_blocks(4 * n_vectors * n_subspaces, 1, PQL_THREADS, 1024);   // backward: upper bound
     return (int64_t)nblk * n_subspaces * n_codewords * d_code * (int64_t)sizeof(float);
 }
 
@@ -560,7 +586,7 @@ static int pq_loss_forward_any(const float *z, const float *table, float *loss, 
     if (codes && (seq_length <= 0 || n_heads <= 0 || n_vectors % ((int64_t)seq_length * n_heads) != 0))
         return SPT_ESHAPE;
     const int total = (int)(n_vectors * parts * n_subspaces);
-    const int nblk = pq_loss_blocks(total);
+    const int nblk = pq_loss_blocks(total, n_subspaces);
     const size_t lds = (size_t)n_subspaces * (n_codewords * d_code + 4) * sizeof(float);
     const float inv_count = 1.0f / ((float)(n_vectors * n_subspaces) * (float)d_code);
     float *partial = reinterpret_cast<float *>(workspace);
@@ -633,7 +659,7 @@ static int pq_loss_backward_any(const float *z, const float *table, const float 
         return SPT_EINVAL;
     if (!pq_loss_shape_ok(n_vectors * parts, n_subspaces, n_codewords, d_code)) return SPT_EUNSUP;
     const int total = (int)(n_vectors * parts * n_subspaces);
-    const int nblk = pq_backward_blocks(total);
+    const int nblk = pq_backward_blocks(total, n_subspaces);
     const bool four = pq_backward_lanes() == 4;
     const int CD = n_codewords * d_code;
     const size_t lds = ((size_t)n_subspaces * ((four ? 4 : 2) * pq_part_stride(d_code, four ? 4 : 2) + 4) +

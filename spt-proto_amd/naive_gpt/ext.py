@@ -447,7 +447,7 @@ def pq_loss_supported(z: torch.Tensor, table: torch.Tensor) -> bool:
     M, C, D = table.shape
     return (z.is_cuda and z.dtype == torch.float32 and table.dtype == torch.float32
             and z.size(-1) == M * D and C == 16 and D in (4, 8)
-            and 0 < M <= 32 and (M & (M - 1)) == 0 and z.numel() > 0)
+            and 0 < M <= 32 and z.numel() > 0)
 
 
 def _pq_loss_args(z: torch.Tensor, table: torch.Tensor):
@@ -693,7 +693,7 @@ def attention_mfma_prepare(indices: torch.Tensor, seq_length: int,
     B, nnz = indices.shape
     lib = load_library()
     size = lib.spt_attention_mfma_tiles_bytes(B, int(seq_length), nnz, layout)
-    _require(size > 0, 'attention_mfma: unsupported shape (d_head 64, Z <= 256, Z % 4 == 0, S <= 2048)')
+    _require(size > 0, 'attention_mfma: unsupported shape (Z <= 256, Z % 4 == 0, S <= 2048)')
     with _on(dev):
         buf = torch.empty([size], dtype=torch.uint8, device=dev)
         rc = lib.spt_attention_mfma_prepare(indices.data_ptr(), buf.data_ptr(), B, int(seq_length),
@@ -732,7 +732,7 @@ def attention_mfma_forward(tiles, q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     N, S, H, E = q.shape
     B = N * H
     if isinstance(tiles, torch.Tensor):
-        _require(E in (64, 128), 'attention_mfma: d_head 64 or 128')
+        _require(E in (64, 80, 128), 'attention_mfma: d_head 64, 80 or 128')
         tiles = attention_mfma_prepare(tiles, S)
     _require(tiles.batch == B and tiles.seq == S, 'tiles: prepared for [N * H, nnz] indices at S')
     dev = _same_device(tiles.buffer, q, k, v)

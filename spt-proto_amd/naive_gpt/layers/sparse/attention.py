@@ -374,7 +374,7 @@ class _SparseCore:
                                          csr_indices.size(-1)):
             # scores, softmax and the product with v run as one launch in _sparse_apply
             ext.note_path('attention', 'fused_gather', fallback=True,
-                          why=lambda: 'q {}: the matrix-core kernels take d_head 64 / 128, S % 32 == 0, S <= 2048'.format(
+                          why=lambda: 'q {}: the matrix-core kernels take d_head 64 / 80 / 128, S % 32 == 0, S <= 2048'.format(
                               tuple(q.shape)))
             return 'fused', indptr, csr_indices, q, k
         ext.note_path('attention', 'operators_head_layout', fallback=True, why=lambda: 'q {}'.format(tuple(q.shape)))
@@ -388,10 +388,10 @@ class _SparseCore:
             return self._sparse_attn_heads(q, k)
         if q.dtype != torch.float32:
             raise RuntimeError('sparse attention: {} tensors only on the matrix-core path (cuda, '
-                               'PQ v2, d_head 64 / 128, S <= 2048, S % 32 == 0)'.format(q.dtype))
+                               'PQ v2, d_head 64 / 80 / 128, S <= 2048, S % 32 == 0)'.format(q.dtype))
         seq_length = q.size(1)
         ext.note_path('attention', 'operators', fallback=q.is_cuda,
-                      why=lambda: 'q {} {}, PQ {}: the fast paths take n * h >= 32, d_head 64 / 128, PQ v2'.format(
+                      why=lambda: 'q {} {}, PQ {}: the fast paths take n * h >= 32, d_head 64 / 80 / 128, PQ v2'.format(
                           tuple(q.shape), q.dtype, self.quantizer.method))
         q = q.transpose(1, 2).contiguous()
         k = k.transpose(1, 2).contiguous()

@@ -22,6 +22,8 @@
 // twice (grad_K, grad_V), spt_csr_transpose + spt_spmm_transposed let callers share it.
 #include "gather4.h"
 #include "sparse_rows.h"
+#include "mfma_tiles.h"
+#include <stdlib.h>
 
 namespace spt {
 
@@ -882,10 +884,25 @@ static int64_t product_scratch_bytes(int B, int S, int E, int nnz) {
     return (int64_t)B * nnz * (int64_t)sizeof(float);                 // permuted values
 }
 
-// the dense-tile form on the matrix cores (mfma_attention.hip)
-bool spmm_mfma_takes(int B, int S, int E, int nnz);
-int spmm_mfma_launch(const int32_t *indptr, const int32_t *indices, const float *values, const float *x,
-                     float *y, int B, int S, int E, int nnz, int x_heads, int y_heads, hipStream_t s);
+// ---- the dense-tile form on the matrix cores: spmm_mfma_kernel (spmm_mfma.hip) ----
+// The shapes of the matrix-core spmm (non-transposed); everything else is for the gather form
+// above.  All S keys of a row stripe are multiplied: worth it from a density of 1 / 16
+// (lookup: 1 / 8); a row's first 64 entries live in registers: mean row length <= 64.
+static bool spmm_mfma_takes(int B, int S, int E, int nnz) {
+    if ((E != 64 && E != 128) || S < 64 || S > MA_MAXNT * MA_KT || B <= 0 || nnz <= 0) return false;
+    if ((long long)nnz * 16 < (long long)S * S || (long long)nnz > 64ll * S) return false;
+    // OPT-IN (SPT_SPMM_MFMA=1): measured at the configs[1] shape (256 slices x 512 x 64, 64 entries per
+    // row; profiles/r04_ops_kernels.txt) this form takes 65.7 us against the gather form's 46.3 -- see
+    // the kernel's header for where they go -- so the gather form stays the default.
+    const char *on = getenv("SPT_SPMM_MFMA");
+    return on && on[0] == '1';
+}
+static int spmm_mfma_launch(const int32_t *indptr, const int32_t *indices, const float *values, const float *x,
+                            float *y, int B, int S, int E, int nnz, int x_heads, int y_heads, hipStream_t s) {
+    if (!spmm_mfma_takes(B, S, E, nnz)) return SPT_EUNSUP;
+    return E == 64 ? launch_spmm_mfma(indptr, indices, values, x, y, B, S, nnz, x_heads, y_heads, s)
+                   : e128::launch_spmm_mfma(indptr, indices, values, x, y, B, S, nnz, x_heads, y_heads, s);
+}
 
 }  // namespace spt
 

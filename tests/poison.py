@@ -38,7 +38,7 @@ FLOAT_ONLY = {
     'embedding_rows_backward': 'routing.hip:361 fp64 per-position partials',
 }
 INDEXED = {
-    'attention_mfma_prepare': 'mfma_attention.hip:2125 tile header, column lists and counts',
+    'attention_mfma_prepare': 'attention_tiles.hip: spt_attention_mfma_prepare tile header, masks and cell counts',
     'csr_transpose': 'spmm.hip:894 the transposed CSR: row pointers and column ids',
     'spmm_forward_cuda': 'spmm.hip:945 a csr_transpose structure in front of the products',
     'grouped_gemm_fused': 'grouped_gemm.hip:2208 ReLU-fix queue counters and entries',

@@ -11,10 +11,12 @@ from test_poison_coverage import EXT, launching_entries
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), 'spt-proto_amd', 'csrc')
 TIERS = ('test_gpu_exact_arithmetic.py', 'test_gpu_arith_contract.py')
-# entries whose matrix-core form is dispatched from a C entry in another (gather) file
+# entries whose matrix-core form is dispatched from a C entry in another (gather) file, or whose own
+# file issues no MFMA although they are a stage of a matrix-core path
 ELSEWHERE = {
     'sddmm_forward_cuda': 'sddmm.hip dispatches to the dense-stripe form of sddmm_tile.hip',
-    'spmm_forward_cuda': 'spmm.hip dispatches to spmm_mfma_kernel of mfma_attention.hip (SPT_SPMM_MFMA=1)',
+    'spmm_forward_cuda': 'spmm.hip dispatches to spmm_mfma_kernel of spmm_mfma.hip (SPT_SPMM_MFMA=1)',
+    'attention_mfma_prepare': 'attention_tiles.hip builds the cell tiles the kernels of mfma_attention.hip read',
 }
 
 EXEMPT = {
@@ -23,13 +25,22 @@ EXEMPT = {
 }
 
 
+def _unit_text(name, seen):
+    """The text of a csrc file and, transitively, of the local headers it includes."""
+    if name in seen or not os.path.exists(os.path.join(CSRC, name)):
+        return ''
+    seen.add(name)
+    text = open(os.path.join(CSRC, name)).read()
+    return text + ''.join(_unit_text(h, seen) for h in re.findall(r'#include\s+"([\w.]+)"', text))
+
+
 def _c_files():
-    """C entry name -> True when its source file issues MFMAs."""
+    """C entry name -> True when its source file, or a local header it includes, issues MFMAs."""
     out = {}
     for name in os.listdir(CSRC):
         if not name.endswith('.hip'):
             continue
-        text = open(os.path.join(CSRC, name)).read()
+        text = _unit_text(name, set())
         mfma = '__builtin_amdgcn_mfma' in text or 'v_mfma' in text
         for c in re.findall(r'extern "C"[^(]*?\b(spt_\w+)\s*\(', text):
             out[c] = mfma

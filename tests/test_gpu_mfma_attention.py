@@ -325,7 +325,7 @@ def test_mfma_unsupported_shapes_are_refused():
 def test_cell_tiles_hold_the_multiplicity_of_every_live_cell():
     """spt_attention_mfma_prepare: per (32-row, 32-key) tile the count of each (row, col) cell in
     the accumulator permutation (byte form when some count is >= 2, else 32-bit row masks), as
-    documented in mfma_attention.hip."""
+    documented in mfma_tiles.h."""
     import numpy as np
     from naive_gpt import ext
     gen = torch.Generator().manual_seed(9)

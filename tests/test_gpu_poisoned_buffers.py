@@ -6,8 +6,8 @@ Each case of CASES runs twice under the `zero` pattern and once under `nan` and 
 * DET cases give the same bits twice under `zero`; their poisoned runs must give the same bits
   again, in every output.
 * ATOMIC cases sum with float atomics in no fixed order (grad_table of cdist.hip:178, grad_k /
-  grad_v of mfma_attention.hip:1793/1852): their poisoned runs must be NaN-free and pass the same
-  reference check as the `zero` run.
+  grad_v of mfma_attention.hip: attention_mfma_backward_keys_kernel): their poisoned runs must be
+  NaN-free and pass the same reference check as the `zero` run.
 
 The class is part of the registry: a DET case that starts to vary fails.  The `zero` run is
 compared with an fp64 or oracle reference, and where the mathematics gives exact zeros (empty

@@ -1,4 +1,4 @@
-"""GPU tier: `kernels.spmm`'s matrix-core form (csrc/mfma_attention.hip: spmm_mfma_kernel; opt-in through
+"""GPU tier: `kernels.spmm`'s matrix-core form (csrc/spmm_mfma.hip: spmm_mfma_kernel; opt-in through
 SPT_SPMM_MFMA=1, which the library reads at every call) against the CPU oracle and against the default
 fp32 gather form, at shapes that take it -- asserted through `ext.paths_taken`.
 

@@ -2,6 +2,9 @@
 -Rpass-analysis=kernel-resource-usage remarks (cross-compiles; no GPU needed).
 
     python tools/resource_usage.py mfma_attention.hip [-DMA_E_VALUE=128 ...] [--grep rows]
+
+(mfma_attention.hip and spmm_mfma.hip are built once per d_head: -DMA_E_VALUE=128 / 80 give the other
+builds; the cell-tile kernels are in attention_tiles.hip.)
 """
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

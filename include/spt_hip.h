@@ -763,6 +763,29 @@ int spt_tall_tn_batch(int count, const float *const *wides, long long ldw, const
                       long long ldn, const int32_t *gather, const int32_t *offsets, int n_groups,
                       long long rows, int width, int n, float *const *outs, int transposed,
                       void *workspace, void *stream);
+/* spt_tall_tn_batch (no gather, no groups) whose problems may read a norm's INPUT where the product
+ * takes the norm's output, and may carry a second narrow operand for the same pass over `wide`:
+ *   rstds[i] != NULL: wides[i] holds s, the input of a LayerNorm (means[i], rstds[i]: [rows], as
+ *     spt_add_layernorm_forward wrote them; gammas[i], betas[i]: [width]) or of an RMS norm (means[i]
+ *     NULL; betas[i] NULL: 0), and every element enters the product as
+ *     fma((s - mean) * rstd, gamma, beta): the bits spt_add_layernorm_forward stores in y, so
+ *     outs[i] has the bits of spt_tall_tn on y -- without the launch that writes y or its memory.
+ *     rstds[i] == NULL (means[i], gammas[i], betas[i] NULL too): wides[i] is read as it is.  rstds
+ *     NULL: no problem has a norm (means, gammas, betas NULL).
+ *   n2 != 0, narrows2[i] != NULL: outs2[i] = wides[i]^T . narrows2[i] ([rows, n2], leading dimension
+ *     ldn2) from the same pass, as [width][n2] or (transposed2 = 1) [n2][width]; narrows2[i] == NULL
+ *     (outs2[i] NULL too): problem i has none.  n2 == 0: narrows2, outs2 NULL.
+ * Every accumulator is the FMA chain over the rows of its own operand in the order of spt_tall_tn, and
+ * the chunks are added in the same order: outs[i] and outs2[i] have the bits of separate spt_tall_tn
+ * calls.  (n, n2): (16, 0), (48, 0), (16, 4), else SPT_EUNSUP.  `transposed` (0 .. 2) is that of
+ * spt_tall_tn for outs.  Alignment as spt_tall_tn; narrows2 16-byte aligned, ldn2 a multiple of 4,
+ * gammas / betas 8-byte aligned.  workspace: count * spt_tall_tn_workspace_bytes(rows, 1, width,
+ * n + n2) bytes. */
+int spt_tall_tn_norm(int count, const float *const *wides, long long ldw, const float *const *narrows,
+                     long long ldn, const float *const *narrows2, long long ldn2, int n2,
+                     const float *const *means, const float *const *rstds, const float *const *gammas,
+                     const float *const *betas, long long rows, int width, int n, float *const *outs,
+                     int transposed, float *const *outs2, int transposed2, void *workspace, void *stream);
 /* spt_tall_tn with a bf16 `wide` (widened on load) and a bf16 `out` [n_groups][width][n] (layout 0), each
  * element rounded once (RNE) after the same in-order reduction of fp32 chunk sums: bitwise reproducible.
  * narrow stays fp32 (ldn % 4 == 0, 16-byte aligned); wide 4-byte aligned, width and ldw even; n % 4 == 0,

@@ -22,6 +22,7 @@
 // rsqrt(var + eps)); row sums are butterfly trees, so results differ from the library's in the
 // last bits only.
 #include "spt_common.h"
+#include "norm_apply.h"
 
 namespace spt {
 
@@ -92,10 +93,10 @@ __global__ __launch_bounds__(LN_THREADS) void add_layernorm_forward_kernel(
             float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (!RMS) b4 = GREG ? bt[j] : reinterpret_cast<const float4 *>(beta)[lane + 64 * j];
             float4 o;
-            o.x = fmaf((v[j].x - mu) * rs, g4.x, b4.x);
-            o.y = fmaf((v[j].y - mu) * rs, g4.y, b4.y);
-            o.z = fmaf((v[j].z - mu) * rs, g4.z, b4.z);
-            o.w = fmaf((v[j].w - mu) * rs, g4.w, b4.w);
+            o.x = ln_apply(v[j].x, mu, rs, g4.x, b4.x);
+            o.y = ln_apply(v[j].y, mu, rs, g4.y, b4.y);
+            o.z = ln_apply(v[j].z, mu, rs, g4.z, b4.z);
+            o.w = ln_apply(v[j].w, mu, rs, g4.w, b4.w);
             yp[lane + 64 * j] = o;
         }
         if (lane == 0) {

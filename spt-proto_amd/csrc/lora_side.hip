@@ -33,6 +33,7 @@
 //              it would be the bound (21-42 us), which is why it is an option.
 // The split image (hi / lo bf16 of x) is written by the same pass in both forms.
 #include "spt_common.h"
+#include "norm_apply.h"
 #include <type_traits>
 
 namespace spt {
@@ -401,30 +402,51 @@ struct TnBatch {
     const float *narrow[TN_BATCH];
     float *out[TN_BATCH];
 };
+// What a problem of the batch may have on top (spt_tall_tn_norm), each pointer null where it does not:
+//   rstd set: `wide` holds the INPUT of a norm and the product takes the norm's output, formed in
+//   registers as the input is loaded (ln_apply: the bits add_layernorm_forward_kernel stores; mean null
+//   = RMS norm, beta null = 0) -- the backward of a layer behind a norm whose output was not kept
+//   (layers/tuning/recompute.py) needs neither the recompute launch nor the tensor;
+//   narrow2 set: a second narrow operand [rows, N2] for the same pass over `wide`, with its own output.
+// Every (column, j) accumulator is a chain of FMAs over the rows of its own operand alone, so each
+// output has the bits of the separate call.
+struct TnSide {
+    const float *mean[TN_BATCH];
+    const float *rstd[TN_BATCH];
+    const float *gamma[TN_BATCH];
+    const float *beta[TN_BATCH];
+    const float *narrow2[TN_BATCH];
+    float *out2[TN_BATCH];
+};
 
 // BF16 (spt_tall_tn_bf16): `wide` holds bf16, widened on load (two columns = 4 bytes per lane); `narrow`
 // has n <= N columns (the rest of the chunk's N are zero)
-template <int N, int UNROLL, bool GATHER, bool BF16>
+// N2, NORM (spt_tall_tn_norm): TnSide's second operand (partial [chunk][N + N2][W]) and norm on load
+template <int N, int UNROLL, bool GATHER, bool BF16, int N2 = 0, bool NORM = false>
 __device__ __forceinline__ void tall_tn_partial(
     TnBatch batch, long long ldw, long long ldn,
     const int32_t *__restrict__ gather, const int32_t *__restrict__ offsets, int G, long long R, int W,
-    float *__restrict__ partial, int n) {
+    float *__restrict__ partial, int n, const TnSide &side = TnSide{}, long long ldn2 = 0) {
     constexpr int JB = N < 16 ? N : 16;                      // table columns per reduction pass
+    constexpr int NT = N + N2;
+    static_assert(N2 <= JB && N2 % 4 == 0 && !(BF16 && (N2 || NORM)), "second operand: one reduction pass, fp32");
     __shared__ float2 red[TN_WAVES][JB][64];
     const float *__restrict__ wide = batch.wide[blockIdx.z];
     const float *__restrict__ narrow = batch.narrow[blockIdx.z];
-    partial += (size_t)blockIdx.z * gridDim.x * N * W;
+    partial += (size_t)blockIdx.z * gridDim.x * NT * W;
+    const float *__restrict__ narrow2 = N2 ? side.narrow2[blockIdx.z] : nullptr;
+    const float *__restrict__ rstd = NORM ? side.rstd[blockIdx.z] : nullptr;   // (both wave-uniform)
     int g, rows; long long row0;
     tn_chunk(offsets, G, R, blockIdx.x, g, row0, rows);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int col0 = blockIdx.y * TN_COLS;
     const int col = min(col0 + 2 * lane, W - 2);             // (clamped lanes are never stored)
-    float acc[2][N];
+    float acc[2][NT];
 #pragma unroll
     for (int c = 0; c < 2; c++)
 #pragma unroll
-        for (int j = 0; j < N; j++) acc[c][j] = 0.0f;
+        for (int j = 0; j < NT; j++) acc[c][j] = 0.0f;
     const int wr0 = wave * TN_RW;                            // this wave's rows of the chunk
     const int wrows = min(TN_RW, rows - wr0);                // (<= 0: nothing, g < 0: rows = 0)
     // the next batch of rows is requested before the current one is used -- and the first one
@@ -448,15 +470,37 @@ __device__ __forceinline__ void tall_tn_partial(
     // the chunk's rows of `narrow` -> LDS (the memory of `red`, free until the sums are formed):
     // read from there as wave-wide broadcasts.  (As scalar loads every row was a miss of the
     // scalar cache -- a 64-byte line used once -- in the middle of the FMA chain: 12 us for 33 MB.)
-    float *nar = reinterpret_cast<float *>(&red[0][0][0]);   // [rows][N]
-    static_assert(sizeof(red) >= (size_t)TN_RC * N * sizeof(float), "narrow chunk fits in red");
+    float *nar = reinterpret_cast<float *>(&red[0][0][0]);   // [rows][N] (with a second operand: [rows][N | N2])
+    static_assert(sizeof(red) >= (size_t)TN_RC * (NT + 2) * sizeof(float), "narrow chunk fits in red");
+    float2 *stat = reinterpret_cast<float2 *>(nar + TN_RC * NT);   // [rows] (mean, rstd) of the norm
+    float2 gm = make_float2(0.f, 0.f), bt = make_float2(0.f, 0.f);  // the lane's two columns
+    if constexpr (NORM) {
+        if (rstd) {
+            const float *mean = side.mean[blockIdx.z], *beta = side.beta[blockIdx.z];
+            gm = *reinterpret_cast<const float2 *>(side.gamma[blockIdx.z] + col);
+            if (beta) bt = *reinterpret_cast<const float2 *>(beta + col);
+            for (int i = threadIdx.x; i < rows; i += 64 * TN_WAVES)
+                stat[i] = make_float2(mean ? mean[row0 + i] : 0.0f, rstd[row0 + i]);
+        }
+    }
+    if constexpr (N2 > 0) {
+        // (a problem without a second operand multiplies by zeros and stores nothing of it: as a branch
+        // around these products in the row loop it cost 110 registers and half the occupancy)
+        for (int i = threadIdx.x; i < rows * (N2 / 4); i += 64 * TN_WAVES) {
+            const int r = i / (N2 / 4), q = i - r * (N2 / 4);
+            reinterpret_cast<float4 *>(nar)[r * (NT / 4) + N / 4 + q] =
+                narrow2 ? *reinterpret_cast<const float4 *>(narrow2 + (row0 + r) * ldn2 + 4 * q)
+                        : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     for (int i = threadIdx.x; i < rows * (N / 4); i += 64 * TN_WAVES) {
         const int r = i / (N / 4), q = i - r * (N / 4);
         const long long src = GATHER ? (long long)gather[row0 + r] : row0 + r;
+        const int at = N2 ? r * (NT / 4) + q : i;
         if (BF16 && 4 * q >= n)
-            reinterpret_cast<float4 *>(nar)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            reinterpret_cast<float4 *>(nar)[at] = make_float4(0.f, 0.f, 0.f, 0.f);
         else
-            reinterpret_cast<float4 *>(nar)[i] = *reinterpret_cast<const float4 *>(narrow + src * ldn + 4 * q);
+            reinterpret_cast<float4 *>(nar)[at] = *reinterpret_cast<const float4 *>(narrow + src * ldn + 4 * q);
     }
     __syncthreads();
     if (wrows > 0) {
@@ -465,12 +509,24 @@ __device__ __forceinline__ void tall_tn_partial(
 #pragma unroll
             for (int u = 0; u < UNROLL; u++) v[u] = vn[u];
             if (r0 + UNROLL < wrows) request(r0 + UNROLL);
+            if constexpr (NORM) {
+                // the batch's rows -> norm outputs, before the products (a clamped row's is not 0: its
+                // weight 0 is applied below, after this)
+                if (rstd) {
+#pragma unroll
+                    for (int u = 0; u < UNROLL; u++) {
+                        const float2 ms = stat[wr0 + min(r0 + u, wrows - 1)];   // the same address in every lane
+                        v[u].x = ln_apply(v[u].x, ms.x, ms.y, gm.x, bt.x);
+                        v[u].y = ln_apply(v[u].y, ms.x, ms.y, gm.y, bt.y);
+                    }
+                }
+            }
 #pragma unroll
             for (int u = 0; u < UNROLL; u++) {
                 if (r0 + u >= wrows) v[u] = make_float2(0.0f, 0.0f);
-                const float4 *np = reinterpret_cast<const float4 *>(nar + (wr0 + min(r0 + u, wrows - 1)) * N);
+                const float4 *np = reinterpret_cast<const float4 *>(nar + (wr0 + min(r0 + u, wrows - 1)) * NT);
 #pragma unroll
-                for (int j4 = 0; j4 < N / 4; j4++) {
+                for (int j4 = 0; j4 < NT / 4; j4++) {
                     const float4 b = np[j4];                 // the same address in every lane
                     acc[0][4 * j4 + 0] = fmaf(v[u].x, b.x, acc[0][4 * j4 + 0]);
                     acc[1][4 * j4 + 0] = fmaf(v[u].y, b.x, acc[1][4 * j4 + 0]);
@@ -486,7 +542,7 @@ __device__ __forceinline__ void tall_tn_partial(
     }
     __syncthreads();                                         // `nar` is read: `red` may be written
     // the eight waves' sums through LDS, JB table columns at a time; partial [chunk][N][W]
-    float *pp = partial + (size_t)blockIdx.x * N * W;
+    float *pp = partial + (size_t)blockIdx.x * NT * W;
 #pragma unroll
     for (int jb = 0; jb < N; jb += JB) {
         if (jb) __syncthreads();
@@ -502,6 +558,33 @@ __device__ __forceinline__ void tall_tn_partial(
             if (c < W) *reinterpret_cast<float2 *>(pp + (size_t)(jb + jj) * W + c) = t;
         }
     }
+    if constexpr (N2 > 0) {
+        // the second operand's columns: one more pass of the same form (rows N .. of the chunk's partial;
+        // without a second operand they stay unwritten and the reduction does not read them)
+        if (narrow2) {
+            __syncthreads();
+#pragma unroll
+            for (int jj = 0; jj < N2; jj++) red[wave][jj][lane] = make_float2(acc[0][N + jj], acc[1][N + jj]);
+            __syncthreads();
+            for (int o = threadIdx.x; o < N2 * 64; o += 64 * TN_WAVES) {
+                const int jj = o >> 6, pair = o & 63;
+                float2 t = red[0][jj][pair];
+#pragma unroll
+                for (int w = 1; w < TN_WAVES; w++) { t.x += red[w][jj][pair].x; t.y += red[w][jj][pair].y; }
+                const int c = col0 + 2 * pair;
+                if (c < W) *reinterpret_cast<float2 *>(pp + (size_t)(N + jj) * W + c) = t;
+            }
+        }
+    }
+}
+
+// spt_tall_tn_norm: no gather, no groups
+template <int N, int N2, int UNROLL>
+__global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_norm_kernel(
+    TnBatch batch, TnSide side, long long ldw, long long ldn, long long ldn2, long long R, int W,
+    float *__restrict__ partial) {
+    tall_tn_partial<N, UNROLL, false, false, N2, true>(batch, ldw, ldn, nullptr, nullptr, 1, R, W, partial, N,
+                                                       side, ldn2);
 }
 
 template <int N, int UNROLL, bool GATHER>
@@ -525,12 +608,16 @@ __global__ __launch_bounds__(64 * TN_WAVES, 2) void tall_tn_partial_bf16_kernel(
 // summation tree.  (One thread per element: 16 K threads on 64 CUs, 8 us for 4 MB.)
 // (BF16: out holds bf16, each element rounded once; `n` is the chunks' padded column count, nout <= n
 // the table's, layout 0 only)
-template <bool BF16>
+// (TWO: the chunks hold n = n1 + n2 columns, columns n1 .. belong to out2 [W][n2] or, transposed2, [n2][W];
+// out2 null: they were not written and are not read)
+template <bool BF16, bool TWO = false>
 __device__ __forceinline__ void tall_tn_reduce(
     const float *__restrict__ partial, const int32_t *__restrict__ offsets, int G, int W, int n,
-    int nchunks, TnBatch batch, int transposed, int nout) {
+    int nchunks, TnBatch batch, int transposed, int nout, int n1 = 0, float *__restrict__ out2 = nullptr,
+    int transposed2 = 0) {
     __shared__ float slice_sum[4][64];
     float *__restrict__ out = batch.out[blockIdx.z];
+    const int n_live = TWO && !out2 ? n1 : n;                // columns of the chunks that are read
     partial += (size_t)blockIdx.z * nchunks * n * W;
     const int g = blockIdx.y;
     const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
@@ -545,7 +632,7 @@ __device__ __forceinline__ void tall_tn_reduce(
     const int per = (count + 3) / 4;
     const int c0 = min(slice * per, count), c1 = min(c0 + per, count);
     float a[4] = {0.f, 0.f, 0.f, 0.f};
-    if (e < W * n) {
+    if (e < W * n_live) {
         const size_t step = (size_t)W * n;
         const float *p = partial + (size_t)first * step + e;
         int c = c0;
@@ -560,13 +647,22 @@ __device__ __forceinline__ void tall_tn_reduce(
     }
     slice_sum[slice][lane] = (a[0] + a[1]) + (a[2] + a[3]);
     __syncthreads();
-    if (slice == 0 && e < W * n) {
+    if (slice == 0 && e < W * n_live) {
         const float v = (slice_sum[0][lane] + slice_sum[1][lane]) + (slice_sum[2][lane] + slice_sum[3][lane]);
         const int j = e / W, w = e - j * W;
         // layout 0: [w][j]; 1: [j][w]; 2: [j / 16][w][16] (rank-16 tables side by side: each its own matrix)
         if constexpr (BF16) {
             if (j < nout) {
                 reinterpret_cast<unsigned short *>(out)[((size_t)g * W + w) * nout + j] = ls_bf_round(v);
+            }
+        } else if constexpr (TWO) {
+            if (j < n1) {
+                const size_t at = transposed == 1 ? (size_t)e
+                                : transposed == 2 ? ((size_t)(j >> 4) * W + w) * 16 + (j & 15)
+                                                  : (size_t)w * n1 + j;
+                out[at] = v;
+            } else {
+                out2[transposed2 ? (size_t)(j - n1) * W + w : (size_t)w * (n - n1) + (j - n1)] = v;
             }
         } else {
             const size_t at = transposed == 1 ? (size_t)e
@@ -581,6 +677,13 @@ __global__ __launch_bounds__(256) void tall_tn_reduce_kernel(
     const float *__restrict__ partial, const int32_t *__restrict__ offsets, int G, int W, int n,
     int nchunks, TnBatch batch, int transposed) {
     tall_tn_reduce<false>(partial, offsets, G, W, n, nchunks, batch, transposed, n);
+}
+
+__global__ __launch_bounds__(256) void tall_tn_reduce_two_kernel(
+    const float *__restrict__ partial, int W, int n1, int n2, int nchunks, TnBatch batch, TnSide side,
+    int transposed, int transposed2) {
+    tall_tn_reduce<false, true>(partial, nullptr, 1, W, n1 + n2, nchunks, batch, transposed, n1 + n2, n1,
+                                side.out2[blockIdx.z], transposed2);
 }
 
 __global__ __launch_bounds__(256) void tall_tn_reduce_bf16_kernel(
@@ -655,6 +758,64 @@ extern "C" int spt_tall_tn_batch(int count, const float *const *wides, long long
                                  void *stream) {
     return tall_tn_any(count, wides, ldw, narrows, ldn, gather, offsets, n_groups, rows, width, n, outs,
                        transposed, workspace, stream);
+}
+
+extern "C" int spt_tall_tn_norm(int count, const float *const *wides, long long ldw,
+                                const float *const *narrows, long long ldn, const float *const *narrows2,
+                                long long ldn2, int n2, const float *const *means, const float *const *rstds,
+                                const float *const *gammas, const float *const *betas, long long rows,
+                                int width, int n, float *const *outs, int transposed, float *const *outs2,
+                                int transposed2, void *workspace, void *stream) {
+    if (count <= 0 || count > TN_BATCH || !wides || !narrows || !outs || !workspace) return SPT_EINVAL;
+    if (rows <= 0 || width <= 0 || n <= 0 || n2 < 0 || ldw < width || ldn < n) return SPT_EINVAL;
+    if (n2 ? (!narrows2 || !outs2 || ldn2 < n2) : (narrows2 || outs2)) return SPT_EINVAL;
+    if (rstds ? !gammas : (means || gammas || betas)) return SPT_EINVAL;
+    if (!((n == 16 || n == 48) && n2 == 0) && !(n == 16 && n2 == 4)) return SPT_EUNSUP;
+    if (transposed < 0 || transposed > 2 || transposed2 < 0 || transposed2 > 1) return SPT_EINVAL;
+    if (rows > 0x7FFFFFFFll) return SPT_EUNSUP;
+    if (width % 2 != 0 || ldw % 2 != 0 || ldn % 4 != 0 || ldn2 % 4 != 0) return SPT_ESHAPE;
+    TnBatch batch = {};
+    TnSide side = {};
+    for (int i = 0; i < count; i++) {
+        if (!wides[i] || !narrows[i] || !outs[i]) return SPT_EINVAL;
+        if ((reinterpret_cast<uintptr_t>(wides[i]) & 7) != 0 || !ls_aligned(narrows[i])) return SPT_ESHAPE;
+        batch.wide[i] = wides[i]; batch.narrow[i] = narrows[i]; batch.out[i] = outs[i];
+        if (n2 && narrows2[i]) {
+            if (!outs2[i]) return SPT_EINVAL;
+            if (!ls_aligned(narrows2[i])) return SPT_ESHAPE;
+            side.narrow2[i] = narrows2[i]; side.out2[i] = outs2[i];
+        } else if (n2 && outs2[i]) {
+            return SPT_EINVAL;
+        }
+        if (rstds && rstds[i]) {
+            if (!gammas[i]) return SPT_EINVAL;
+            // (the lane's two columns of gamma and beta are one 8-byte load)
+            if ((reinterpret_cast<uintptr_t>(gammas[i]) & 7) != 0 ||
+                (betas && betas[i] && (reinterpret_cast<uintptr_t>(betas[i]) & 7) != 0))
+                return SPT_ESHAPE;
+            side.rstd[i] = rstds[i]; side.gamma[i] = gammas[i];
+            side.mean[i] = means ? means[i] : nullptr;
+            side.beta[i] = betas ? betas[i] : nullptr;
+        } else if ((means && means[i]) || (gammas && gammas[i]) || (betas && betas[i])) {
+            return SPT_EINVAL;
+        }
+    }
+    const int nchunks = (int)((rows + TN_RC - 1) / TN_RC);
+    hipStream_t s = (hipStream_t)stream;
+    float *partial = static_cast<float *>(workspace);
+    const dim3 grid(nchunks, (width + TN_COLS - 1) / TN_COLS, count);
+#define SPT_TNN(N, N2, U)                                                                               \
+    hipLaunchKernelGGL((tall_tn_partial_norm_kernel<N, N2, U>), grid, dim3(64 * TN_WAVES), 0, s, batch, side, \
+                       ldw, ldn, ldn2, rows, width, partial)
+    if (n2) SPT_TNN(16, 4, 8);
+    else if (n == 16) SPT_TNN(16, 0, 8);
+    else SPT_TNN(48, 0, 4);
+#undef SPT_TNN
+    SPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(tall_tn_reduce_two_kernel, dim3((width * (n + n2) + 63) / 64, 1, count), dim3(256), 0, s,
+                       partial, width, n, n2, nchunks, batch, side, transposed, transposed2);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
 }
 
 extern "C" long long spt_tall_tn_bf16_workspace_bytes(long long rows, int n_groups, int width, int n) {

@@ -127,6 +127,9 @@ _PROTOTYPES = {
     'spt_tall_tn_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
     'spt_tall_tn_batch': ([_c_int, _c_ptr, ctypes.c_longlong, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, _c_int,
                            ctypes.c_longlong, _c_int, _c_int, _c_ptr, _c_int, _c_ptr, _c_ptr], _c_int),
+    'spt_tall_tn_norm': ([_c_int, _c_ptr, ctypes.c_longlong, _c_ptr, ctypes.c_longlong, _c_ptr, ctypes.c_longlong,
+                          _c_int] + [_c_ptr] * 4 + [ctypes.c_longlong, _c_int, _c_int, _c_ptr, _c_int, _c_ptr,
+                                                    _c_int, _c_ptr, _c_ptr], _c_int),
     'spt_tall_tn': ([_c_ptr, ctypes.c_longlong, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, _c_int,
                      ctypes.c_longlong, _c_int, _c_int, _c_ptr, _c_int, _c_ptr, _c_ptr], _c_int),
     'spt_route_topk': ([_c_ptr] * 5 + [_c_int] * 3 + [_c_ptr], _c_int),
@@ -1499,13 +1502,49 @@ def tall_tn_supported(wide: torch.Tensor, narrow: torch.Tensor) -> bool:
             and narrow.stride(0) % 4 == 0 and narrow.data_ptr() % 16 == 0)
 
 
+def tall_tn_norm_supported(wide: torch.Tensor, narrow: torch.Tensor, norm=None, narrow2: torch.Tensor = None) -> bool:
+    """`tall_tn(wide, narrow, norm=norm, narrow2=narrow2)` runs: n = 16 or 48, or 16 with a second
+    operand of 4 columns; the norm's statistics one per row, its parameters one per column."""
+    if not tall_tn_supported(wide, narrow):
+        return False
+    rows, width = wide.shape
+    n = narrow.size(1)
+    if narrow2 is not None:
+        if not (n == 16 and tall_tn_supported(wide, narrow2) and narrow2.size(1) == 4 and narrow2.size(0) == rows
+                and narrow2.device == wide.device):
+            return False
+    elif n not in (16, 48):
+        return False
+    if norm is not None:
+        mean, rstd, gamma, beta = norm
+        for t, count in ((mean, rows), (rstd, rows), (gamma, width), (beta, width)):
+            if t is not None and not (t.dtype == torch.float32 and t.device == wide.device and t.is_contiguous()
+                                      and t.numel() == count and t.data_ptr() % 8 == 0):
+                return False
+        if rstd is None or gamma is None:
+            return False
+    return narrow.size(0) == rows
+
+
 def tall_tn(wide: torch.Tensor, narrow: torch.Tensor, gather: torch.Tensor = None,
-            offsets: torch.Tensor = None, transposed: bool = False, split16: bool = False) -> torch.Tensor:
+            offsets: torch.Tensor = None, transposed: bool = False, split16: bool = False,
+            norm=None, narrow2: torch.Tensor = None, transposed2: bool = False):
     """``spt_tall_tn``: wide^T . narrow -> [G, width, n] (``transposed``: [G, n, width];
     ``split16``: [G, n / 16, width, 16], one contiguous matrix per rank-16 table); G = 1
     without ``offsets``, else the row groups offsets[g] .. offsets[g + 1] (device int32).
-    ``gather`` [rows] int32 picks the row of ``narrow`` for every row of ``wide``."""
+    ``gather`` [rows] int32 picks the row of ``narrow`` for every row of ``wide``.
+
+    ``norm`` = (mean, rstd, gamma, beta) (``spt_tall_tn_norm``): ``wide`` is the INPUT of a norm and the
+    product takes the norm's output, formed on load -- the bits of
+    ``tall_tn(add_layernorm_forward(wide, ...)[1], narrow)`` without that launch and tensor (mean None:
+    RMS norm, beta None: 0).  ``narrow2`` [rows, 4]: a second product from the same pass; the result is
+    then the pair (out, out2), out2 [1, width, 4] or (``transposed2``) [1, 4, width].  Neither takes
+    ``gather`` or ``offsets`` (`tall_tn_norm_supported`)."""
     _require(not (transposed and split16), 'tall_tn: transposed or split16')
+    if norm is not None or narrow2 is not None:
+        _require(gather is None and offsets is None, 'tall_tn: norm / narrow2 without gather and offsets')
+        return tall_tn_batch([wide], [narrow], norms=[norm], narrows2=[narrow2], transposed2=transposed2,
+                             layout=2 if split16 else int(transposed))[0]
     _require(tall_tn_supported(wide, narrow), 'tall_tn: fp32 CUDA [rows, even width] x [*, 4 | 16 | 48]')
     rows, width = wide.shape
     n = narrow.size(1)
@@ -1542,15 +1581,56 @@ def tall_tn_batchable(wides, narrows) -> bool:
                for w, nr in zip(wides, narrows))
 
 
-def tall_tn_batch(wides, narrows, gather: torch.Tensor = None, offsets: torch.Tensor = None):
+def tall_tn_batch(wides, narrows, gather: torch.Tensor = None, offsets: torch.Tensor = None,
+                  norms=None, narrows2=None, transposed2: bool = False, layout: int = 0):
     """``spt_tall_tn_batch``: the `tall_tn` results [G, width, n] of 1 .. 4 (wide, narrow) pairs of one
     shape and one pair of row strides (`tall_tn_batchable`), sharing `gather` and `offsets`: one
-    pair of launches for all of them."""
+    pair of launches for all of them.
+
+    ``norms`` / ``narrows2`` (``spt_tall_tn_norm``): per pair the `norm` / `narrow2` of `tall_tn` or
+    None; a pair with a second operand gives the pair (out, out2) in place of out.  ``layout``: 0
+    [1, width, n], 1 [1, n, width], 2 [1, n / 16, width, 16] for every out."""
     count = len(wides)
     _require(tall_tn_batchable(wides, narrows), 'tall_tn_batch: 1 .. 4 supported pairs of one shape')
     w0, n0 = wides[0], narrows[0]
     rows, width = w0.shape
     n = n0.size(1)
+    if norms is not None or narrows2 is not None:
+        norms = [None] * count if norms is None else list(norms)
+        narrows2 = [None] * count if narrows2 is None else list(narrows2)
+        _require(gather is None and offsets is None, 'tall_tn_batch: norms / narrows2 without gather and offsets')
+        _require(len(norms) == count and len(narrows2) == count, 'tall_tn_batch: one norm / narrow2 (or None) per pair')
+        _require(all(tall_tn_norm_supported(w, nr, nm, n2) for w, nr, nm, n2 in zip(wides, narrows, norms, narrows2)),
+                 'tall_tn_batch: norm on load takes n = 16 | 48 | 16 + 4, fp32 statistics per row, parameters per column')
+        two = [t for t in narrows2 if t is not None]
+        _require(all(t.stride(0) == two[0].stride(0) for t in two), 'narrows2: one row stride')
+        _require(layout in (0, 1, 2) and (layout != 2 or n % 16 == 0), 'layout: 0, 1 or 2 (n % 16 == 0)')
+        dev = w0.device
+        lib = load_library()
+        array = ctypes.c_void_p * count
+        n2 = 4 if two else 0
+
+        def ptrs(ts):
+            return array(*[None if t is None else t.data_ptr() for t in ts])
+        mean, rstd, gamma, beta = [[None if nm is None else nm[i] for nm in norms] for i in range(4)]
+        normed = any(nm is not None for nm in norms)
+        with _on(dev):
+            shape = [[1, width, n], [1, n, width], [1, n // 16, width, 16]][layout]
+            out = torch.empty([count] + shape, dtype=torch.float32, device=dev)
+            out2 = torch.empty([count, 1, 4, width] if transposed2 else [count, 1, width, 4], dtype=torch.float32,
+                               device=dev) if two else None
+            work = torch.empty([count * lib.spt_tall_tn_workspace_bytes(rows, 1, width, n + n2)], dtype=torch.uint8,
+                               device=dev)
+            rc = lib.spt_tall_tn_norm(
+                count, ptrs(wides), w0.stride(0), ptrs(narrows), n0.stride(0),
+                ptrs(narrows2) if two else None, two[0].stride(0) if two else 0, n2,
+                ptrs(mean) if normed else None, ptrs(rstd) if normed else None, ptrs(gamma) if normed else None,
+                ptrs(beta) if normed else None, rows, width, n, ptrs(out.unbind(0)), layout,
+                ptrs([None if t is None else out2[i] for i, t in enumerate(narrows2)]) if two else None,
+                int(transposed2), work.data_ptr(), _stream(dev))
+        if rc != 0:
+            _raise(lib, rc, 'tall_tn_norm')
+        return [out[i] if t is None else (out[i], out2[i]) for i, t in enumerate(narrows2)]
     G = 1 if offsets is None else offsets.numel() - 1
     if gather is not None:
         _check_type(gather, torch.int32, 'gather')

@@ -25,6 +25,10 @@ class _AddLayerNorm(torch.autograd.Function):
         s, y, mean, rstd = ext.add_layernorm_forward(x.contiguous(), r.contiguous(), gamma, beta, eps, rms)
         ctx.save_for_backward(s, gamma, mean, rstd)
         ctx.rms = rms
+        # (for recompute.tag: a consumer that recomputes y on load needs the row statistics, which are
+        # not outputs of this node -- as non-differentiable outputs their zero gradients would be two
+        # more fills per backward)
+        y._spt_norm_stats = (mean, rstd)
         return s, y
 
     @staticmethod
@@ -47,6 +51,7 @@ class _LayerNorm(torch.autograd.Function):
         _, y, mean, rstd = ext.add_layernorm_forward(x, None, gamma, beta, eps, rms)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.rms = rms
+        y._spt_norm_stats = (mean, rstd)
         return y
 
     @staticmethod

@@ -636,19 +636,23 @@ def _route(x: torch.Tensor, rw: torch.Tensor, rb, n_blocks: int, k: int):
     return prob, bk, bk.block.int()
 
 
+def _route_dlogit(grad_coeff, prob, bk: Buckets, block):
+    """d coeff [P] -> d logit [T, nb]: the adjoint of the bucketing chained through the sigmoid"""
+    nb = bk.n_blocks
+    if grad_coeff.is_cuda and nb <= 8:
+        return ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
+    dprob = torch.zeros_like(prob)
+    dprob.view(-1).index_put_((bk.token_long * nb + bk.block,), 2.0 * grad_coeff)
+    return dprob * (1.0 - prob) * prob
+
+
 def _route_backward(ctx, grad_coeff, prob, bk: Buckets, block, x, rw, grad_x):
     """The router's share of the backward: d coeff [P] -> d logit [T, nb] (one launch: the adjoint of
     the bucketing chained through the sigmoid), its input gradient ADDED into `grad_x` (the FFN's
     own, same tensor: one sum inside one autograd node), and the gradients of its weight and bias.
     -> (grad_rw, grad_rb)."""
     from naive_gpt.layers.tuning.lora import tall_tn
-    nb = bk.n_blocks
-    if grad_coeff.is_cuda and nb <= 8:
-        dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
-    else:
-        dprob = torch.zeros_like(prob)
-        dprob.view(-1).index_put_((bk.token_long * nb + bk.block,), 2.0 * grad_coeff)
-        dlogit = dprob * (1.0 - prob) * prob
+    dlogit = _route_dlogit(grad_coeff, prob, bk, block)
     grad_x.addmm_(dlogit, rw)
     grad_rw = tall_tn(dlogit, x) if ctx.needs_input_grad[1] else None       # [nb, d]
     grad_rb = dlogit.sum(dim=0) if ctx.needs_input_grad[2] else None
@@ -674,7 +678,7 @@ class RoutedLoRAFFN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, nb: int, top_k: int, act: int,
-                origin_input=None, origin_module=None):
+                origin_input=None, origin_module=None, origin_lazy=None):
         d_ff, d = w1.shape
         x = x.contiguous()
         bs, rank = d_ff // nb, l1.size(1)
@@ -724,15 +728,20 @@ class RoutedLoRAFFN(torch.autograd.Function):
         ctx.bk, ctx.act = bk, act
         # x is a norm output the block can recompute: keep its origin instead (tuning/recompute.py)
         ctx.origin_module = origin_module
+        # (recompute.lazy: the backward reads x in two table gradients alone, and they can form it from
+        # the norm's input as they load it)
+        ctx.lazy = origin_module is not None and origin_lazy is not None
         ctx.save_for_backward(x if origin_module is None else origin_input, coeff, u, h, s, z,
-                              l1, r1, l2, r2, w1, w2, prob, block, rw)
+                              l1, r1, l2, r2, w1, w2, prob, block, rw, *(origin_lazy.norm if ctx.lazy else ()))
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, coeff, u, h, s, z, l1, r1, l2, r2, w1, w2, prob, block, rw = ctx.saved_tensors
+        x, coeff, u, h, s, z, l1, r1, l2, r2, w1, w2, prob, block, rw = ctx.saved_tensors[:15]
+        norm = tuple(ctx.saved_tensors[15:19]) if ctx.lazy else None
         if ctx.origin_module is not None:
-            x = recompute.output(ctx.origin_module, x).view(-1, w1.size(1))
+            # x: the norm's INPUT from here on; its output is formed on load or recomputed below
+            x = x.view(-1, w1.size(1))
         bk, act = ctx.bk, ctx.act
         nb = bk.n_blocks
         d_ff, d = w1.shape
@@ -758,27 +767,54 @@ class RoutedLoRAFFN(torch.autograd.Function):
         du_tok = ext.rows_combine(du, bk.pos)                                # [T, r]: du[pos].sum(1)
         # (two pairs of equal shape: one pair of launches each)
         from naive_gpt.layers.tuning.lora import tall_tn_many
-        grad_l1, grad_r2 = tall_tn_many([(x, du_tok), (dy, ext.rows_combine(z, bk.pos))])
+        z_tok = ext.rows_combine(z, bk.pos)
+        router_rides = grad_coeff.is_cuda and nb <= 8 and d % 4 == 0
+        dlogit = grad_rw = None
+        if router_rides:
+            dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
+        if ctx.origin_module is not None:
+            # The two readers of x are the gradients of L1 (x^T du) and of the router's weight (dlogit^T x).
+            # From the norm's input, statistics and parameters one pass forms x on load and feeds both
+            # (ext.tall_tn_batch: norms, narrows2); anything else recomputes the tensor as before.
+            want_rw = router_rides and ctx.needs_input_grad[1]
+            if norm is not None and router_rides and x.size(0) >= 512 \
+                    and ext.tall_tn_batchable([x, dy], [du_tok, z_tok]) \
+                    and ext.tall_tn_norm_supported(x, du_tok, norm, dlogit if want_rw else None):
+                ext.note_path('norm_output', 'on_load')
+                ext.note_path('tall_tn', 'kernel_batch')
+                outs = ext.tall_tn_batch([x, dy], [du_tok, z_tok], norms=[norm, None],
+                                         narrows2=[dlogit, None] if want_rw else None, transposed2=True)
+                if want_rw:
+                    outs[0], grad_rw = outs[0][0], outs[0][1][0]                    # [nb, d]
+                grad_l1, grad_r2 = outs[0][0], outs[1][0]
+                x = None                                                             # (not read again)
+            else:
+                ext.note_path('norm_output', 'recomputed', fallback=norm is not None,
+                              why=lambda: 'routed FFN: x {} rank {} blocks {}'.format(tuple(x.shape), rank, nb))
+                x = recompute.output(ctx.origin_module, x).view(-1, w1.size(1))
+        if x is not None:
+            grad_l1, grad_r2 = tall_tn_many([(x, du_tok), (dy, z_tok)])
+        del z_tok
         grad_r1, grad_l2 = _tn_blocks_many([(ds, u), (h, dzt)], bk)
         del dot_main, dot_act, du_tok, dzt
         dxs = ext.grouped_gemm_fused(
             ds, w1, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
             n_rows=rows, rowscale=coeff, a2=du, b2=l1, b2_group_stride=0)
         del ds, du
-        if grad_coeff.is_cuda and nb <= 8 and d % 4 == 0:
+        if router_rides:
             # the router's share d logit . W_r of grad_x inside the un-bucketing pass
-            dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
             grad_x = ext.rows_combine(dxs, bk.pos, side=dlogit, side_weight=rw.contiguous())
             del dxs
-            from naive_gpt.layers.tuning.lora import tall_tn
-            grad_rw = tall_tn(dlogit, x) if ctx.needs_input_grad[1] else None   # [nb, d]
+            if x is not None and ctx.needs_input_grad[1]:
+                from naive_gpt.layers.tuning.lora import tall_tn
+                grad_rw = tall_tn(dlogit, x)                                        # [nb, d]
             grad_rb = dlogit.sum(dim=0) if ctx.needs_input_grad[2] else None
         else:
             grad_x = ext.rows_combine(dxs, bk.pos)
             del dxs
             grad_rw, grad_rb = _route_backward(ctx, grad_coeff, prob, bk, block, x, rw, grad_x)
         return (grad_x, grad_rw, grad_rb, grad_l1, grad_r1, grad_l2, grad_r2,
-                None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None)
 
 
 def routed_lora_ffn(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks: int, top_k: int, act: int,
@@ -787,7 +823,7 @@ def routed_lora_ffn(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks: int, to
     if origin is None:
         return RoutedLoRAFFN.apply(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks, top_k, act)
     return RoutedLoRAFFN.apply(x, rw, rb, l1, r1, l2, r2, w1, b1, w2, b2, n_blocks, top_k, act,
-                               origin.input, origin.module)
+                               origin.input, origin.module, recompute.lazy(origin))
 
 
 def _images_usable(a: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, d: int, bs: int) -> bool:
@@ -816,7 +852,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, nb: int, top_k: int, activation,
-                origin_input=None, origin_module=None):
+                origin_input=None, origin_module=None, origin_lazy=None):
         d_ff, d = wg.shape
         x = x.contiguous()
         prob, bk, block = _route(x, rw, rb, nb, top_k)
@@ -858,16 +894,20 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
         y = ext.rows_combine(ys, bk.pos)
         ctx.bk, ctx.activation = bk, activation
         ctx.origin_module = origin_module
+        ctx.lazy = origin_module is not None and origin_lazy is not None      # (as RoutedLoRAFFN)
         ctx.save_for_backward(x if origin_module is None else origin_input, coeff, ug, us, g, sd,
-                              h, z, lg, rg, ls, rs, ld, rd, wg, ws, wd, prob, block, rw)
+                              h, z, lg, rg, ls, rs, ld, rd, wg, ws, wd, prob, block, rw,
+                              *(origin_lazy.norm if ctx.lazy else ()))
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (x, coeff, ug, us, g, sd, h, z, lg, rg, ls, rs, ld, rd, wg, ws, wd, prob, block,
-         rw) = ctx.saved_tensors
+         rw) = ctx.saved_tensors[:20]
+        norm = tuple(ctx.saved_tensors[20:24]) if ctx.lazy else None
         if ctx.origin_module is not None:
-            x = recompute.output(ctx.origin_module, x).view(-1, wg.size(1))
+            # x: the norm's INPUT from here on; its output is formed on load or recomputed below
+            x = x.view(-1, wg.size(1))
         bk, activation = ctx.bk, ctx.activation
         nb = bk.n_blocks
         d_ff, d = wg.shape
@@ -899,7 +939,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
         grad_coeff = (dot_h - (dz_rows * z).sum(dim=-1)) / _floor(coeff)
 
         def down(dpre, pre, w, u, l_table, r_table, dot_pre=None, into=None):
-            """-> (dx rows [P, d], d coefficient [P], grad of the two LoRA tables)"""
+            """-> (dx rows [P, d], d coefficient [P], du per token [T, r], grad of the `right` table)"""
             du, _ = _down_blocks(dpre, r_table, bk, False)
             u_rows = u.index_select(0, bk.token_long)
             if dot_pre is None:
@@ -910,22 +950,46 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
                 dpre, w, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
                 n_rows=rows, rowscale=coeff, a2=du, b2=l_table, b2_group_stride=0,
                 out=into, accumulate=into is not None)
-            grad_l = _tn(x, ext.rows_combine(du, bk.pos))
             grad_r = _tn_blocks(dpre, u, bk)
-            return dxs, dc, grad_l, grad_r
+            return dxs, dc, ext.rows_combine(du, bk.pos), grad_r
 
-        dxs_g, dc_g, grad_lg, grad_rg = down(dg, g, wg, ug, lg, rg, dot_g)
+        dxs_g, dc_g, du_g, grad_rg = down(dg, g, wg, ug, lg, rg, dot_g)
         del dg
-        dxs_g, dc_s, grad_ls, grad_rs = down(dsd, sd, ws, us, ls, rs, dot_s, into=dxs_g)
+        dxs_g, dc_s, du_s, grad_rs = down(dsd, sd, ws, us, ls, rs, dot_s, into=dxs_g)
         del dsd
         grad_x = ext.rows_combine(dxs_g, bk.pos)
         del dxs_g
         grad_coeff = grad_coeff + dc_g + dc_s
-        grad_rw, grad_rb = _route_backward(ctx, grad_coeff, prob, bk, block, x, rw, grad_x)
+        dlogit = _route_dlogit(grad_coeff, prob, bk, block)
+        grad_x.addmm_(dlogit, rw)                                            # (as _route_backward)
+        # The readers of x: the two `left` gradients and the router's weight gradient.  From the norm's
+        # input, statistics and parameters one pair of launches forms x on load for all three
+        # (ext.tall_tn_batch: norms, narrows2); anything else recomputes the tensor as before.
+        want_rw = ctx.needs_input_grad[1]
+        grad_rw = None
+        if ctx.origin_module is not None:
+            if norm is not None and x.size(0) >= 512 and ext.tall_tn_batchable([x, x], [du_g, du_s]) \
+                    and ext.tall_tn_norm_supported(x, du_g, norm, dlogit if want_rw else None):
+                ext.note_path('norm_output', 'on_load')
+                ext.note_path('tall_tn', 'kernel_batch')
+                outs = ext.tall_tn_batch([x, x], [du_g, du_s], norms=[norm, norm],
+                                         narrows2=[dlogit, None] if want_rw else None, transposed2=True)
+                if want_rw:
+                    outs[0], grad_rw = outs[0][0], outs[0][1][0]                    # [nb, d]
+                grad_lg, grad_ls = outs[0][0], outs[1][0]
+                x = None
+            else:
+                ext.note_path('norm_output', 'recomputed', fallback=norm is not None,
+                              why=lambda: 'gated routed FFN: x {} rank {} blocks {}'.format(tuple(x.shape), rank, nb))
+                x = recompute.output(ctx.origin_module, x).view(-1, wg.size(1))
+        if x is not None:
+            grad_lg, grad_ls = _tn(x, du_g), _tn(x, du_s)
+            grad_rw = _tn(dlogit, x) if want_rw else None                        # [nb, d]
+        grad_rb = dlogit.sum(dim=0) if ctx.needs_input_grad[2] else None
         grad_ld = _tn_blocks(h, dzt, bk)
         grad_rd = _tn(dy, ext.rows_combine(z, bk.pos))
         return (grad_x, grad_rw, grad_rb, grad_lg, grad_rg, grad_ls, grad_rs, grad_ld, grad_rd,
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 def routed_lora_llama_ffn(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks: int, top_k: int,
@@ -934,7 +998,7 @@ def routed_lora_llama_ffn(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_block
         return RoutedLoRALLaMAFFN.apply(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks, top_k,
                                         activation)
     return RoutedLoRALLaMAFFN.apply(x, rw, rb, lg, rg, ls, rs, ld, rd, wg, ws, wd, n_blocks, top_k,
-                                    activation, origin.input, origin.module)
+                                    activation, origin.input, origin.module, recompute.lazy(origin))
 
 
 # ---------------------------------------------------------------- the LoRA routed FFNs on bf16 storage

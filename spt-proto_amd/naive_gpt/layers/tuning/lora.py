@@ -374,7 +374,12 @@ class _FrozenLoRAQKV(torch.autograd.Function):
             outs.append(y.view(*x.shape[:-1], n))
         origin = recompute.origin_of(x)
         ctx.origin_module = origin.module if origin is not None else None
-        ctx.save_for_backward(origin.input if origin is not None else x2, u3, *weights, *lefts, *rights)
+        # (the backward reads x in the `left` gradients alone: with the norm's statistics and parameters
+        # that product forms x from the norm's input as it loads it, and nothing is recomputed)
+        lazy = recompute.lazy(origin)
+        ctx.lazy = lazy is not None
+        ctx.save_for_backward(origin.input if origin is not None else x2, u3, *weights, *lefts, *rights,
+                              *(lazy.norm if lazy is not None else ()))
         ctx.x_shape = x.shape
         return tuple(outs)
 
@@ -385,8 +390,10 @@ class _FrozenLoRAQKV(torch.autograd.Function):
         x2, u3 = saved[0], saved[1]
         weights, lefts, rights = saved[2:5], saved[5:8], saved[8:11]
         n, k = weights[0].shape
+        norm = tuple(saved[11:15]) if ctx.lazy else None
         if ctx.origin_module is not None:
-            x2 = recompute.output(ctx.origin_module, x2).reshape(-1, k)
+            # x2: the norm's INPUT from here on; its output is formed on load or recomputed where it is read
+            x2 = x2.reshape(-1, k)
         rows = x2.size(0)
         one = _one_group(rows, x2.device)
         dy2 = [None if d is None else d.reshape(-1, n).contiguous() for d in dys]
@@ -435,7 +442,16 @@ class _FrozenLoRAQKV(torch.autograd.Function):
                 grad_x = grad_x.view(ctx.x_shape)
         grad_lefts, grad_rights = [None] * 3, [None] * 3
         if live:
-            if r == 16 and ext.tall_tn_supported(x2, du_cat) and x2.size(0) >= 512:
+            on_load = norm is not None and r == 16 and rows >= 512 and ext.tall_tn_norm_supported(x2, du_cat, norm)
+            if ctx.origin_module is not None:
+                ext.note_path('norm_output', 'on_load' if on_load else 'recomputed',
+                              fallback=norm is not None and not on_load,
+                              why=lambda: 'q / k / v: {} live gradients of rank {}, {} rows'.format(len(live), r, rows))
+                if not on_load:
+                    x2 = recompute.output(ctx.origin_module, x2).reshape(-1, k)
+            if on_load:
+                gl = ext.tall_tn(x2, du_cat, split16=True, norm=norm)[0]       # x2: the norm's input
+            elif r == 16 and ext.tall_tn_supported(x2, du_cat) and x2.size(0) >= 512:
                 gl = ext.tall_tn(x2, du_cat, split16=True)[0]                  # [len(live), k, 16]
             else:
                 gl = tall_tn(x2, du_cat).view(x2.size(1), len(live), r).permute(1, 0, 2)

@@ -12,8 +12,15 @@ layers' autograd functions (``lora._FrozenLoRALinear``, ``grouped.RoutedLoRAFFN`
 the tagged tensor's origin instead of the tensor and call ``output`` in their backward, which
 recomputes it once and hands the same tensor to the consumers that follow (q, k, v).
 
+A consumer whose backward reads the norm output only in its table gradients (``spt_tall_tn``) does not
+need the tensor at all: ``lazy`` gives it the norm's input, statistics and parameters, and the product
+forms the output's elements as it loads the input (``ext.tall_tn(..., norm=...)``: same bits, no
+recompute launch, no 33.5 MB write and read back).
+
 No reference counterpart: the reference keeps every activation (plain autograd).
 """
+import collections
+
 import torch
 from torch import nn
 
@@ -21,10 +28,17 @@ _RECOMPUTABLE = (nn.LayerNorm,)
 
 
 class Origin:
-    __slots__ = ('module', 'input')
+    __slots__ = ('module', 'input', 'stats')
 
-    def __init__(self, module, input):
-        self.module, self.input = module, input
+    def __init__(self, module, input, stats=None):
+        # stats: (mean, rstd) [rows] of the norm's node when the kernel computed the output (fused_norm.py)
+        self.module, self.input, self.stats = module, input, stats
+
+
+# What `ext.tall_tn(s, narrow, norm=lazy.norm)` needs in place of the norm output.  mean, beta: None for
+# an RMS norm.
+Lazy = collections.namedtuple('Lazy', 's mean rstd gamma beta rms')
+Lazy.norm = property(lambda self: (self.mean, self.rstd, self.gamma, self.beta))
 
 
 def register(cls):
@@ -43,12 +57,28 @@ def tag(output: torch.Tensor, module: nn.Module, input: torch.Tensor) -> torch.T
     release()
     if torch.is_grad_enabled() and input.requires_grad and isinstance(module, _RECOMPUTABLE) \
             and input.is_cuda and not input.is_inference():
-        output._spt_origin = Origin(module, input)
+        output._spt_origin = Origin(module, input, getattr(output, '_spt_norm_stats', None))
     return output
 
 
 def origin_of(t: torch.Tensor):
     return getattr(t, '_spt_origin', None)
+
+
+def lazy(origin):
+    """The norm output behind `origin` as (s, mean, rstd, gamma, beta, rms) -- nothing is launched -- or
+    None where there is no origin or the norm did not run as the kernel (no statistics): `output` then.
+    Consumers keep the tensors with save_for_backward."""
+    if origin is None or origin.stats is None:
+        return None
+    from ..basic import fused_norm
+    kind = fused_norm._kind(origin.module)
+    if kind is None:
+        return None
+    gamma, beta, _, rms = kind
+    mean, rstd = origin.stats
+    return Lazy(origin.input, None if rms else mean, rstd, gamma.detach(), None if beta is None else beta.detach(),
+                rms)
 
 
 _last = [None, None]          # (key, tensor): the norm output most recently recomputed

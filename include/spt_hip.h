@@ -187,7 +187,7 @@ int spt_sddmm_forward(const int32_t *indptr, const int32_t *indices,
  * (nnz >= S * S / 16, mean row length <= 64, d_head 64 or 128, 64 <= S <= 2048) are multiplied as DENSE
  * 32 x 32 tiles on the matrix cores: a wave assembles the tile of its 32 rows in LDS from the CSR
  * entries (duplicates add) and contracts it with the bf16 image of x (split-bf16, <= 2^-15 relative
- * error per product; csrc/mfma_attention.hip: spmm_mfma_kernel).  Opt-in because it is SLOWER at the
+ * error per product; csrc/spmm_mfma.hip: spmm_mfma_kernel).  Opt-in because it is SLOWER at the
  * benchmark shape (65.7 against 46.3 us, profiles/r04_ops_kernels.txt; the kernel's header says
  * where the time goes).  spt_spmm_form() tells which form a call would take (1 = matrix cores,
  * 0 = gather).
@@ -335,7 +335,7 @@ int spt_attention_mfma_supported(int seq_length, int d_head, int nnz);
  * spt_attention_mfma_prepare buckets the CSR entries of every 32-row tile by 32-key tile (one
  * pass over `indices` [batch, nnz]) into `tiles`, an opaque device buffer of
  * spt_attention_mfma_tiles_bytes(...) bytes that the forward and the backward of the same
- * layer step share (it depends on `indices` only; layout: mfma_attention.hip, "cell tiles").
+ * layer step share (it depends on `indices` only; layout: mfma_tiles.h, "cell tiles").
  * Two layouts, the same one to be named in all four calls:
  *   SPT_TILES_FULL     any uniform-row CSR;
  *   SPT_TILES_COMPACT  a quarter of the memory (S = 512: 66 instead of 272 KiB per slice) for

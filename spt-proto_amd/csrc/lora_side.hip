@@ -32,51 +32,15 @@
 //              bf16): 9.0 us for 8192 x 1024 x 16, under the pass's memory time; at 48-64 columns
 //              it would be the bound (21-42 us), which is why it is an option.
 // The split image (hi / lo bf16 of x) is written by the same pass in both forms.
-#include "spt_common.h"
+#include "split_bf16.h"
 #include "norm_apply.h"
 #include <type_traits>
 
 namespace spt {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 ls_bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 ls_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float ls_f32x2;
-__device__ __forceinline__ unsigned short ls_bf_round(float a) {       // RNE
-    const ls_f32x2 x = {a, 0.0f};
-    return (unsigned short)__builtin_bit_cast(unsigned, __builtin_convertvector(x, ls_bf16x2));
-}
-typedef __attribute__((ext_vector_type(2))) __bf16 ls_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float ls_f32x2;
-typedef __attribute__((ext_vector_type(4))) float ls_f32x4;
-
-// two floats -> packed bf16 pairs (first value in the low half): hi = RNE, lo = RNE(x - hi)
-__device__ __forceinline__ void ls_split2(float a, float b, unsigned &hi, unsigned &lo) {
-    const ls_f32x2 x = {a, b};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, ls_bf16x2));
-    const ls_f32x2 hf = {__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x - hf, ls_bf16x2));
-}
-struct LsFrag { uint4 hi, lo; };
-__device__ __forceinline__ LsFrag ls_split8(const float (&v)[8]) {
-    LsFrag f;
-    ls_split2(v[0], v[1], f.hi.x, f.lo.x);
-    ls_split2(v[2], v[3], f.hi.y, f.lo.y);
-    ls_split2(v[4], v[5], f.hi.z, f.lo.z);
-    ls_split2(v[6], v[7], f.hi.w, f.lo.w);
-    return f;
-}
-__device__ __forceinline__ ls_f32x4 ls_mma(const uint4 &a, const uint4 &b, ls_f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(ls_bf16x8, a),
-                                                   __builtin_bit_cast(ls_bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ ls_f32x4 ls_mma3(const LsFrag &a, const LsFrag &b, ls_f32x4 c) {
-    c = ls_mma(a.lo, b.hi, c);
-    c = ls_mma(a.hi, b.lo, c);
-    return ls_mma(a.hi, b.hi, c);
-}
 // exact fp32: lane (r, g) holds a[r][8 g + i] and b[8 g + i][c = r], i = 0 .. 7; MFMA i contracts
 // the four k's {i, 8 + i, 16 + i, 24 + i} of the 32-wide k-step (one per lane group g)
-__device__ __forceinline__ ls_f32x4 ls_mma_f32x8(const float (&a)[8], const float (&b)[8], ls_f32x4 c) {
+__device__ __forceinline__ f32x4 ls_mma_f32x8(const float (&a)[8], const float (&b)[8], f32x4 c) {
 #pragma unroll
     for (int i = 0; i < 8; i++) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i], c, 0, 0, 0);
     return c;
@@ -144,7 +108,7 @@ __global__ __launch_bounds__(64 * LS_NW) void lora_down_kernel(
     const float *xp = x + row * ldx + 32 * sbeg + 8 * g;
     const float *lp = l + (size_t)(32 * sbeg + 8 * g) * n + r;
     char *ip = IMAGE ? image + ((size_t)row * nsteps + sbeg) * 128 + 16 * g : nullptr;
-    ls_f32x4 acc[NB];
+    f32x4 acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; b++) acc[b] = {0.f, 0.f, 0.f, 0.f};
     float ss = 0.f;
@@ -193,11 +157,11 @@ __global__ __launch_bounds__(64 * LS_NW) void lora_down_kernel(
             if (c + 1 < CH) load_l(RAGGED ? min(s0 + c + 1, cnt - 1) : s0 + c + 1, bnext);
             const float av[8] = {a[c][0].x, a[c][0].y, a[c][0].z, a[c][0].w,
                                  a[c][1].x, a[c][1].y, a[c][1].z, a[c][1].w};
-            LsFrag af;
-            if (IMAGE || !EXACT) af = ls_split8(av);
+            Frag af;
+            if (IMAGE || !EXACT) af = split8(av);
 #pragma unroll
             for (int b = 0; b < NB; b++)
-                acc[b] = EXACT ? ls_mma_f32x8(av, bv[b], acc[b]) : ls_mma3(af, ls_split8(bv[b]), acc[b]);
+                acc[b] = EXACT ? ls_mma_f32x8(av, bv[b], acc[b]) : mm<2, 2>(af, split8(bv[b]), acc[b]);
             if (IMAGE && row0 + r < rows) {
                 char *dst = ip + (size_t)(s0 + c) * 128;
                 *reinterpret_cast<uint4 *>(dst) = af.hi;
@@ -653,7 +617,7 @@ __device__ __forceinline__ void tall_tn_reduce(
         // layout 0: [w][j]; 1: [j][w]; 2: [j / 16][w][16] (rank-16 tables side by side: each its own matrix)
         if constexpr (BF16) {
             if (j < nout) {
-                reinterpret_cast<unsigned short *>(out)[((size_t)g * W + w) * nout + j] = ls_bf_round(v);
+                reinterpret_cast<unsigned short *>(out)[((size_t)g * W + w) * nout + j] = round_bf16(v);
             }
         } else if constexpr (TWO) {
             if (j < n1) {

@@ -1,8 +1,7 @@
 // mfma_frag.h -- split-bf16 operand fragments and the bf16 LDS images of 32-row tiles, for one head
 // dimension: what the kernels of mfma_attention.hip and spmm_mfma.hip are written in.
 //
-// fp32 operands are split into two bf16 halves x = hi + lo (hi = RNE(x), lo = RNE(x - hi)) and
-// every product is three MFMAs (lo*hi + hi*lo + hi*hi): relative error <= 2^-16 per product.
+// The split itself (hi / lo parts, three MFMAs per product) is split_bf16.h's.
 //
 // A unit that includes this is compiled once per head dimension: for d_head 64 and, with
 // -DMA_E_VALUE=128 / 80, for d_head 128 / 80.  What it puts between MA_NS_OPEN and MA_NS_CLOSE lands
@@ -12,6 +11,7 @@
 #define SPT_MFMA_FRAG_H
 
 #include "mfma_tiles.h"
+#include "split_bf16.h"
 
 #ifndef MA_E_VALUE
 #define MA_E_VALUE 64
@@ -30,10 +30,6 @@
 #endif
 
 MA_NS_OPEN
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #ifndef MA_THREADS_VALUE
 #define MA_THREADS_VALUE 512
@@ -58,47 +54,6 @@ constexpr int MA_VLD = 72;                         // bytes per e row of V^T: 32
 constexpr int MA_KH = 0, MA_KL = MA_KT * MA_KLD, MA_VH = 2 * MA_KT * MA_KLD,
               MA_VL = 3 * MA_KT * MA_KLD, MA_IMG = 4 * MA_KT * MA_KLD;         // 18432 B
 constexpr int MA_TLD = 36;                         // floats per row of the epilogue's [e][row] tile
-
-struct Split { unsigned hi, lo; };
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-// two floats -> packed bf16 pairs (first value in the low half): hi = RNE, lo = RNE(x - hi).
-// Whole-vector conversions: element-wise (__bf16) casts compile to one v_cvt_pk_bf16_f32 per
-// ELEMENT plus re-packing (81 conversions per tile instead of 24).
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    const f32x2 x = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-}
-__device__ __forceinline__ Split split2(float a, float b) {
-    const f32x2 x = {a, b};
-    Split s;
-    s.hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
-    const f32x2 hf = {__builtin_bit_cast(float, s.hi << 16),
-                      __builtin_bit_cast(float, s.hi & 0xffff0000u)};
-    s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x - hf, bf16x2));
-    return s;
-}
-struct Frag { uint4 hi, lo; };      // 8 bf16 each: one MFMA operand fragment, split
-__device__ __forceinline__ Frag split8(float a0, float a1, float a2, float a3, float a4,
-                                       float a5, float a6, float a7) {
-    const Split s0 = split2(a0, a1), s1 = split2(a2, a3), s2 = split2(a4, a5),
-                s3 = split2(a6, a7);
-    Frag f;
-    f.hi = make_uint4(s0.hi, s1.hi, s2.hi, s3.hi);
-    f.lo = make_uint4(s0.lo, s1.lo, s2.lo, s3.lo);
-    return f;
-}
-__device__ __forceinline__ f32x16 mma(const uint4 &a, const uint4 &b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                   __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// (a.hi + a.lo)(b.hi + b.lo) without the lo*lo term, small terms first.  PA / PB = parts of the
-// operand: 2 = an fp32 value split in two, 1 = a value that IS a bf16 (bf16 storage: no lo part).
-template <int PA, int PB>
-__device__ __forceinline__ f32x16 mm(const Frag &a, const Frag &b, f32x16 c) {
-    if (PA == 2) c = mma(a.lo, b.hi, c);
-    if (PB == 2) c = mma(a.hi, b.lo, c);
-    return mma(a.hi, b.hi, c);
-}
 
 // The lane id, from an instruction the compiler will not move.  For the kernels' RARE branches:
 // whatever such a branch derives from the ordinary `lane` is loop-invariant, gets hoisted out of
@@ -277,12 +232,6 @@ __device__ __forceinline__ Frag read_cols(const char *hi, const char *lo, int ro
 // (All 64 lanes must be active: the gather crosses lanes.)  A half whose upper 16 columns lie
 // beyond E (d_head 80, col0 = 64) reads its lower 16 columns twice: output columns 80 .. 95 of
 // the product are then copies of 64 .. 79 and are never stored.
-typedef short v4s16 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint2 lds_tr_b64(const char *p) {
-    const v4s16 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) v4s16 *)(p));
-    return __builtin_bit_cast(uint2, r);
-}
 template <int NP>
 __device__ __forceinline__ Frag read_cols_tr(const char *hi, const char *lo, int col0, int lane,
                                              int s) {

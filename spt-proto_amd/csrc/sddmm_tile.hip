@@ -41,15 +41,10 @@
 // park (39-41 us: the pickers' ~330 vector instructions per stripe became the critical path); skipping
 // the key tiles right of a stripe's largest column id (causal patterns: half of the MFMAs; the
 // extra control flow cost more waits than the MFMAs saved: 39 us).
-#include "spt_common.h"
+#include "split_bf16.h"
 #include <stdlib.h>
 
 namespace spt {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 st_bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 st_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float st_f32x2;
-typedef __attribute__((ext_vector_type(16))) float st_f32x16;
 
 constexpr int ST_WAVES = 8;
 constexpr int ST_THREADS = 64 * ST_WAVES;
@@ -66,36 +61,6 @@ constexpr int ST_QPART = ST_ROWS * ST_QLD;          // one part (hi or lo)
 constexpr int ST_QIMG = 2 * ST_QPART;
 constexpr int ST_RPW = ST_ROWS / ST_WAVES;          // rows of a stripe a wave picks entries for
 constexpr int ST_LDS = 2 * ST_DBUF * 4 + 2 * ST_QIMG;        // 150,528 B: one workgroup per CU
-
-struct StSplit { unsigned hi, lo; };
-// two floats -> packed bf16 pairs (first value in the low half): hi = RNE, lo = RNE(x - hi)
-__device__ __forceinline__ StSplit st_split2(float a, float b) {
-    const st_f32x2 x = {a, b};
-    StSplit s;
-    s.hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, st_bf16x2));
-    const st_f32x2 hf = {__builtin_bit_cast(float, s.hi << 16), __builtin_bit_cast(float, s.hi & 0xffff0000u)};
-    s.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(x - hf, st_bf16x2));
-    return s;
-}
-struct StFrag { uint4 hi, lo; };
-__device__ __forceinline__ StFrag st_split8(const float4 &a, const float4 &b) {
-    const StSplit s0 = st_split2(a.x, a.y), s1 = st_split2(a.z, a.w), s2 = st_split2(b.x, b.y),
-                  s3 = st_split2(b.z, b.w);
-    StFrag f;
-    f.hi = make_uint4(s0.hi, s1.hi, s2.hi, s3.hi);
-    f.lo = make_uint4(s0.lo, s1.lo, s2.lo, s3.lo);
-    return f;
-}
-__device__ __forceinline__ st_f32x16 st_mma(const uint4 &a, const uint4 &b, st_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(st_bf16x8, a),
-                                                   __builtin_bit_cast(st_bf16x8, b), c, 0, 0, 0);
-}
-// (a.hi + a.lo)(b.hi + b.lo) without the lo * lo term, small terms first
-__device__ __forceinline__ st_f32x16 st_mm(const StFrag &a, const StFrag &b, st_f32x16 c) {
-    c = st_mma(a.lo, b.hi, c);
-    c = st_mma(a.hi, b.lo, c);
-    return st_mma(a.hi, b.hi, c);
-}
 
 struct StPicks { int start[ST_RPW], end[ST_RPW], col[ST_RPW]; };
 #ifdef ST_STAMP
@@ -148,7 +113,7 @@ __device__ __forceinline__ void sddmm_tile_body(
     };
     auto store_q = [&](int s, const float4 &x) {
         char *img = qimg + (s & 1) * ST_QIMG + qrow * ST_QLD + qe4 * 2;
-        const StSplit a = st_split2(x.x, x.y), c = st_split2(x.z, x.w);
+        const Split a = split2(x.x, x.y), c = split2(x.z, x.w);
         *reinterpret_cast<uint2 *>(img) = make_uint2(a.hi, c.hi);
         *reinterpret_cast<uint2 *>(img + ST_QPART) = make_uint2(a.lo, c.lo);
     };
@@ -190,11 +155,11 @@ __device__ __forceinline__ void sddmm_tile_body(
     const float4 q0 = load_q(0), q1 = load_q(1);
     float4 q_a = load_q(2), q_b2;                               // (q_a: the stripe the coming iteration stores)
     StPicks pk_a = request(p0), pk_b = request(p1), pk_c = request(p2), pk_d;
-    StFrag kf[2][ST_KS];
+    Frag kf[2][ST_KS];
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int ks = 0; ks < ST_KS; ks++) kf[t][ks] = st_split8(kraw[t][ks][0], kraw[t][ks][1]);
+        for (int ks = 0; ks < ST_KS; ks++) kf[t][ks] = split8(kraw[t][ks][0], kraw[t][ks][1]);
     store_q(0, q0);
     store_q(1, q1);
     __syncthreads();
@@ -203,7 +168,7 @@ __device__ __forceinline__ void sddmm_tile_body(
     // runs under its MFMAs: `fetch` requests the eight Q fragments (a wave that picks first does
     // that before picking), `scores` contracts the first key tile, starts the second, stores the
     // first while the second's MFMAs run, then stores the second.
-    StFrag qf[ST_KS];
+    Frag qf[ST_KS];
     auto fetch = [&](int s) {
 #ifndef ST_ABL_NO_MMA
         const char *qh = qimg + (s & 1) * ST_QIMG + c32 * ST_QLD + 16 * h;
@@ -218,7 +183,7 @@ __device__ __forceinline__ void sddmm_tile_body(
 #ifndef ST_ABL_NO_MMA
         // lane (i, h) holds row i, keys 8 g + 4 h + u of its tile in register 4 g + u
         float *drow = dbuf + (s & 1) * ST_DBUF + c32 * ST_DLD + wave * ST_WKEYS + 4 * h;
-        auto park = [&](const st_f32x16 &d, int t) {
+        auto park = [&](const f32x16 &d, int t) {
 #ifdef ST_ABL_NO_PARK
             asm volatile("" ::"v"(d));
             return;
@@ -228,17 +193,17 @@ __device__ __forceinline__ void sddmm_tile_body(
                 *reinterpret_cast<float4 *>(drow + 32 * t + 8 * g) =
                     make_float4(d[4 * g], d[4 * g + 1], d[4 * g + 2], d[4 * g + 3]);
         };
-        st_f32x16 d0, d1;
+        f32x16 d0, d1;
 #pragma unroll
         for (int r = 0; r < 16; r++) { d0[r] = 0.f; d1[r] = 0.f; }
 #pragma unroll
-        for (int ks = 0; ks < ST_KS; ks++) d0 = st_mm(kf[0][ks], qf[ks], d0);
-        d1 = st_mm(kf[1][0], qf[0], d1);
+        for (int ks = 0; ks < ST_KS; ks++) d0 = mm<2, 2>(kf[0][ks], qf[ks], d0);
+        d1 = mm<2, 2>(kf[1][0], qf[0], d1);
         __builtin_amdgcn_sched_barrier(0);
         park(d0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 1; ks < ST_KS; ks++) d1 = st_mm(kf[1][ks], qf[ks], d1);
+        for (int ks = 1; ks < ST_KS; ks++) d1 = mm<2, 2>(kf[1][ks], qf[ks], d1);
         park(d1, 1);
 #endif
     };

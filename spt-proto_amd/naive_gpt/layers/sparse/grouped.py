@@ -5,7 +5,7 @@ weights are frozen (the LoRA variants the upgrader installs: the hot path).  Not
 here reads a bucket size on the host: the (token, block) pairs are sorted by block with
 device ops, bucket boundaries stay in a device int32 ``offsets`` tensor, and every
 block GEMM of a layer is ONE launch of ``spt_grouped_gemm`` (fp32 MFMA,
-``spt-proto_amd/csrc/grouped_gemm.hip``) -- compare the reference's loop of boolean-mask
+``spt-proto_amd/csrc/grouped_gemm.hip`` and its units) -- compare the reference's loop of boolean-mask
 gathers and per-block cuBLAS calls (``layers/tuning/lora_ffn.py:87-111``).
 
 Row space: P = T * k rows, row p = the p-th (token, block) pair in block-major order

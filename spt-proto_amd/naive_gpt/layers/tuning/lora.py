@@ -107,7 +107,7 @@ def _one_group(rows: int, device) -> torch.Tensor:
 
 def _mfma_linear_usable(x2: torch.Tensor, weight: torch.Tensor, rank: int, forward: bool = True) -> bool:
     """Shapes for which the frozen product goes through the library's split-bf16 matrix-core
-    GEMM (grouped_gemm.hip with one bucket; ~320 TFLOP/s against ~125 for the fp32 library
+    GEMM (grouped_gemm.hip and its units, with one bucket; ~320 TFLOP/s against ~125 for the fp32 library
     GEMM): fp32, contiguous, the contraction length a multiple of 4 (rows of A are read 16
     bytes at a time), rank inside one k-tile, enough rows to fill the GPU.  The forward
     contracts over in_features, the backward (dX = dY W) over out_features -- a vocabulary of

@@ -1,7 +1,7 @@
 """Inputs the matrix-core kernels must reproduce exactly, and the rounding rules of their contracts.
 
-The fp32 split path (`gg_split2`: hi = RNE(x), lo = RNE(x - hi), a product as hi.hi + hi.lo + lo.hi
-in fp32) is determined bit for bit when
+The fp32 split path (`split2` and `mm` of csrc/split_bf16.h: hi = RNE(x), lo = RNE(x - hi), a product
+as hi.hi + hi.lo + lo.hi in fp32) is determined bit for bit when
   * the operands are integers;
   * one operand of every product has at most 16 significant bits (then hi + lo == x exactly) and the
     other is exact in bf16 (its lo is 0, so the dropped lo.lo is 0);

@@ -27,8 +27,8 @@ PATTERNS = ('zero', 'nan', 'big')
 FLOAT_ONLY = {
     'cdist_backward_cuda': 'cdist.hip:247 per-block fp32 partials of grad_table',
     'spmm_transposed': 'spmm.hip:881-882 fp32 per-chunk outputs or permuted values',
-    'grouped_gemm_wgrad': 'grouped_gemm.hip:2345 fp32 per-chunk partials of dW and dbias (bf16: :2403)',
-    'split_bf16': 'grouped_gemm.hip:1733-1734 split_bf16_kernel stores hi / lo bf16 pairs only',
+    'grouped_gemm_wgrad': 'grouped_wgrad.hip: spt_grouped_gemm_wgrad_workspace_bytes fp32 per-chunk partials of dW and dbias (bf16: the same)',
+    'split_bf16': 'grouped_gemm.hip: split_bf16_kernel stores hi / lo bf16 pairs only',
     'lora_down': 'lora_side.hip:145 the by-product split image: 128-byte hi / lo bf16 blocks',
     'lora_down_tables': 'lora_side.hip:145 (via :340) the by-product split image',
     'lora_down_grouped': 'lora_side.hip:145 (via :349) the by-product split image',
@@ -41,7 +41,7 @@ INDEXED = {
     'attention_mfma_prepare': 'attention_tiles.hip: spt_attention_mfma_prepare tile header, masks and cell counts',
     'csr_transpose': 'spmm.hip:894 the transposed CSR: row pointers and column ids',
     'spmm_forward_cuda': 'spmm.hip:945 a csr_transpose structure in front of the products',
-    'grouped_gemm_fused': 'grouped_gemm.hip:2208 ReLU-fix queue counters and entries',
+    'grouped_gemm_fused': 'grouped_gemm.hip: launch_grouped ReLU-fix queue counters and entries',
 }
 
 _NAN_WORD = 0x7FC00000

@@ -146,7 +146,7 @@ def _gg_fused(images):
                                             n_rows=P, epilogue=ext.EPI_ACT, activation=ext.ACT_RELU,
                                             keep_preact=True, **kw)
             assert ext.LAST_GEMM_PATH == images
-            # the queue's per-segment counters (grouped_gemm.hip:404, one every 16 words)
+            # the queue's per-segment counters (gg_epilogue of grouped_gemm.h, one every 16 words)
             counts = ext.LAST_RELU_QUEUE[:256 * 64].view(torch.int32).view(256, 16)[:, 0].clone()
             return h, pre, counts
 

@@ -1,5 +1,5 @@
 """Grouped GEMM, image path, K = N = 1024, one bucket, at 512 / 1024 / 1536 / 4096 tiles: run under
-SPT_HIP_LIBRARY=<ablation variant> (tools/variant.sh ... grouped_gemm -DGG_ABL_*) to see which stream
+SPT_HIP_LIBRARY=<ablation variant> (tools/variant.sh ... grouped_gemm_img -DGG_ABL_*) to see which stream
 the k-loop waits for."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""-DGR_STAMP build of the ring GEMM (tools/variant.sh rstamp grouped_gemm -DGR_STAMP): per k-step, cycles
+"""-DGR_STAMP build of the ring GEMM (tools/variant.sh rstamp grouped_gemm_ring -DGR_STAMP): per k-step, cycles
 a loader wave waits for FREE / issues its 12 LDS-DMAs / waits for the previous step to land, and a consumer
 waits for FULL (at a tile's first step / at later steps)."""
 import os, sys

@@ -1,5 +1,5 @@
 """Where a wave of the image-path GEMM spends a tile's k-loop (a -DGG_STAMP_DMA build:
-tools/variant.sh stamps grouped_gemm -DGG_STAMP_DMA; run with SPT_HIP_LIBRARY=.../libspt_hip_stamps.so
+tools/variant.sh stamps grouped_gemm_img -DGG_STAMP_DMA; run with SPT_HIP_LIBRARY=.../libspt_hip_stamps.so
 SPT_GEMM_PERSISTENT=0): cycles issuing the step's LDS-DMAs, reading fragments (+ the wait for them),
 in the MFMA groups, parked at the step's barrier -- per tile, median over the waves."""
 import os, sys

@@ -1,6 +1,6 @@
 // Which ingredient of the grouped GEMM's k-loop costs the matrix pipe its time?  8 waves per CU
 // (one 512-thread workgroup), per "k-step" and wave: 24 MFMAs 32x32x16 bf16 on 4 accumulators
-// (chains of 3 on one accumulator, as gg_mma3), optionally fed by 16 ds_read_b128 from an LDS
+// (chains of 3 on one accumulator, as mm<2, 2> of split_bf16.h), optionally fed by 16 ds_read_b128 from an LDS
 // tile (mode bit 0), with a workgroup barrier per step (bit 1), with the reads pipelined half a
 // step ahead (bit 2), with 6 LDS-DMA instructions per wave and step from a 16 MB buffer (bit 3).
 // Prints TFLOP/s per mode.  Build: hipcc -O3 --offload-arch=gfx950.

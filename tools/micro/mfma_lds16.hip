@@ -1,5 +1,5 @@
 // mfma_lds.hip's k-loop once more with v_mfma_f32_16x16x32_bf16: per "k-step" (32 k) and wave
-// 48 MFMAs on 16 accumulators of a 64 x 64 tile (chains of 3, as gg_mma3), fed by the same 16
+// 48 MFMAs on 16 accumulators of a 64 x 64 tile (chains of 3, as mm<2, 2> of split_bf16.h), fed by the same 16
 // ds_read_b128 (row = lane & 15 of a 16-row group, chunk = lane >> 4: conflict-free under the GEMM's
 // swizzle), same modes: reads (1), barrier (2), pipelined (4), LDS-DMA (8).  Same flops per step.
 // Build: hipcc -O3 --offload-arch=gfx950.  Prints TFLOP/s per mode, to be read beside mfma_lds.hip's.

@@ -720,14 +720,20 @@ int spt_cross_entropy_grad(float *logits, long long ld, long long rows, int n_cl
  * LayerNorm of the residual stream with the additions around it (the pre-norm wiring of
  * naive_gpt/layers/basic/transformer.py:46-52; nn.LayerNorm arithmetic: biased variance, eps
  * inside the root), or -- rms != 0 -- LLaMA's RMSNorm (utils.py:22-37: no mean, no beta; beta may be
- * NULL, mean is written as 0, dbeta as 0).  rows x d fp32, contiguous; d in {256, 512, 1024, 2048},
- * RMSNorm also 4096 (SPT_EUNSUP else).
+ * NULL, mean is written as 0, dbeta as 0).  rows x d fp32, contiguous; the widths are those for which
+ * spt_layernorm_form(d, rms) != 0 (SPT_EUNSUP else).
  *   forward   s = x + r (r, s may be NULL: s = x, nothing written);  y = LN(s) gamma + beta;
  *             mean, rstd [rows] for the backward.
  *   backward  dx = dLN(dy) (+ dskip, may be NULL: the gradient arriving over the skip path);
  *             dgamma, dbeta = ONE buffer [2, d] (dbeta == dgamma + d); `partial`:
  *             spt_layernorm_partial_rows(rows) x 2 d floats of scratch.  Fixed summation order.
+ * spt_layernorm_form() (host only, no launch) is the one width gate: 0 = refused, else the number of
+ * waves that share a row -- 1: a wave owns a row (d = 256, 512, 768, 1024, 2048; RMSNorm also 4096),
+ * 2 or 4: the wide-row kernels (d = 2560: 2; d = 5120 and LayerNorm 4096: 4; row sums cross the
+ * waves through LDS in a fixed order).  With SPT_LAYERNORM_WIDE=1 in the environment (read at every
+ * call) RMSNorm 4096 takes the wide form too: kept for measurement (tools/time_layernorm.py).
  */
+int spt_layernorm_form(int d, int rms);
 int spt_layernorm_partial_rows(long long rows);
 int spt_add_layernorm_forward(const float *x, const float *r, const float *gamma, const float *beta,
                               float *s, float *y, float *mean, float *rstd, long long rows, int d,

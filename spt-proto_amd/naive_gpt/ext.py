@@ -109,6 +109,7 @@ _PROTOTYPES = {
     'spt_rows_combine_bf16': ([_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_ffn_coeff_grad': ([_c_ptr, _c_ptr, _c_int] + [_c_ptr] * 6 + [_c_f32, _c_ptr, _c_int, _c_int, _c_ptr],
                            _c_int),
+    'spt_layernorm_form': ([_c_int] * 2, _c_int),
     'spt_layernorm_partial_rows': ([ctypes.c_longlong], _c_int),
     'spt_add_layernorm_forward': ([_c_ptr] * 8 + [ctypes.c_longlong, _c_int, _c_f32, _c_int, _c_ptr], _c_int),
     'spt_layernorm_backward': ([_c_ptr] * 10 + [ctypes.c_longlong, _c_int, _c_int, _c_ptr], _c_int),
@@ -2110,12 +2111,30 @@ def cross_entropy_grad_(logits: torch.Tensor, n_classes: int, target: torch.Tens
     return loss
 
 
-LAYERNORM_WIDTHS = (256, 512, 1024, 2048)
+def layernorm_form(d: int, rms: bool = False) -> int:
+    """``spt_layernorm_form``: 0 = the kernels refuse this width, else the number of waves that
+    share a row (1: a wave per row; 2, 4: the wide-row kernels).  Host only: no launch."""
+    return int(load_library().spt_layernorm_form(int(d), int(bool(rms))))
+
+
+def __getattr__(name):
+    # LAYERNORM_WIDTHS: the LayerNorm widths, asked of the library (csrc/layernorm.hip holds the one
+    # list that decides), so importing this module does not need the library
+    if name == 'LAYERNORM_WIDTHS':
+        return tuple(d for d in range(64, 8193, 64) if layernorm_form(d, False))
+    raise AttributeError('module {!r} has no attribute {!r}'.format(__name__, name))
+
+
+def layernorm_takes(is_cuda: bool, dtype, shape, d: int, rms: bool = False) -> bool:
+    """`layernorm_supported` on a tensor's description: CUDA fp32 [..., d], not empty, d a width of
+    `layernorm_form`."""
+    shape = tuple(shape)
+    return bool(is_cuda and dtype == torch.float32 and len(shape) > 0 and shape[-1] == d
+                and 0 not in shape and layernorm_form(d, rms) > 0)
 
 
 def layernorm_supported(x: torch.Tensor, d: int, rms: bool = False) -> bool:
-    return (x.is_cuda and x.dtype == torch.float32 and x.size(-1) == d and x.numel() > 0
-            and (d in LAYERNORM_WIDTHS or (rms and d == 4096)))
+    return layernorm_takes(x.is_cuda, x.dtype, x.shape, d, rms)
 
 
 def add_layernorm_forward(x: torch.Tensor, r, gamma: torch.Tensor, beta, eps: float, rms: bool = False):
@@ -2124,7 +2143,7 @@ def add_layernorm_forward(x: torch.Tensor, r, gamma: torch.Tensor, beta, eps: fl
     d = x.size(-1)
     _require(layernorm_supported(x, d, rms) and x.is_contiguous() and gamma.is_contiguous()
              and gamma.numel() == d and gamma.dtype == torch.float32,
-             'add_layernorm: contiguous CUDA fp32 [..., d], d in {256, 512, 1024, 2048} (RMS: also 4096)')
+             'add_layernorm: contiguous CUDA fp32 [..., d], d a width that layernorm_form(d, rms) takes')
     if not rms:
         _require(beta is not None and beta.is_contiguous() and beta.numel() == d, 'beta: [d]')
     if r is not None:

@@ -98,7 +98,8 @@ def test_e80_within_the_chain_bound(bf16):
     C.test_attention_mfma_within_the_chain_bound(1, 4, 256, 32, E, bf16)
 
 
-@pytest.mark.parametrize('entry,case', [
+# the registry's attention cases at d_head 80; test_gpu_guard_bands runs them between guard bands too
+E80_CASES = [
     ('attention_mfma_prepare', P.Case('s320_e80_compact', P._mfma(1, 2, 320, 32, E, False, 'bits'), P.ATOMIC)),
     ('attention_mfma_forward', P.Case('s640_e80_yt', P._mfma(1, 2, 640, 64, E, True), P.ATOMIC)),
     ('attention_mfma_forward', P.Case('s2048_z256_e80', P._mfma(1, 1, 2048, 256, E, False), P.ATOMIC)),
@@ -106,7 +107,10 @@ def test_e80_within_the_chain_bound(bf16):
     ('attention_mfma_backward', P.Case('s320_e80_gt', P._mfma(1, 2, 320, 32, E, True), P.ATOMIC)),
     ('attention_mfma_backward', P.Case('s320_e80_bf16', P._mfma(1, 2, 320, 32, E, False, bf16=True), P.ATOMIC)),
     ('attention_mfma_backward', P.Case('s320_e80_bf16_gt', P._mfma(1, 2, 320, 32, E, True, bf16=True), P.ATOMIC)),
-], ids=lambda x: x.name if isinstance(x, P.Case) else x)
+]
+
+
+@pytest.mark.parametrize('entry,case', E80_CASES, ids=lambda x: x.name if isinstance(x, P.Case) else x)
 def test_e80_entry_ignores_what_its_buffers_held(entry, case):
     P.test_entry_ignores_what_its_buffers_held(entry, case)
 

@@ -33,12 +33,19 @@ def _gen(seed):
     return torch.Generator().manual_seed(seed)
 
 
+def _dev(t):
+    """Every operand of every case reaches the device through this one function, so that
+    test_gpu_guard_bands can swap it for guard.home: an input then lies between guard bands, as the
+    wrappers' own allocations do (test_poison_coverage checks that no case bypasses it)."""
+    return t.cuda()
+
+
 def _randn(gen, *shape, dtype=torch.float32):
-    return torch.randn(list(shape), generator=gen).to(dtype).cuda()
+    return _dev(torch.randn(list(shape), generator=gen).to(dtype))
 
 
 def _offsets(sizes):
-    return torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32).cuda()
+    return _dev(torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32))
 
 
 def _close(got, want, name, rtol=1e-4, atol=0.0):
@@ -97,8 +104,8 @@ def _gg_fp32():
     G, n, k, T = len(GG_SIZES), 200, 72, 190          # N % 128 and K % 32 tails
     P = sum(GG_SIZES)
     a, w, bias = _randn(gen, T, k), _randn(gen, G * n, k), _randn(gen, G, n)
-    gather = torch.randint(0, T, [P], generator=gen, dtype=torch.int32).cuda()
-    scale = (torch.rand([P], generator=gen) + 0.5).cuda()
+    gather = _dev(torch.randint(0, T, [P], generator=gen, dtype=torch.int32))
+    scale = _dev(torch.rand([P], generator=gen) + 0.5)
     off = _offsets(GG_SIZES)
 
     def call():
@@ -127,7 +134,7 @@ def _near_kink_operands(gen, K, N):
         for n in range(min(N, KINK_SIZES[g])):
             row, p = g * N + n, offsets[g] + n
             w[row] -= (w[row] @ a[p] - nudge[row]) / (a[p] @ a[p]) * a[p]
-    return a.float().cuda(), w.float().cuda()
+    return _dev(a.float()), _dev(w.float())
 
 
 def _gg_fused(images):
@@ -174,8 +181,8 @@ def _gg_dact():
     P = sum(GG_SIZES)
     a, w = _randn(gen, T, k), _randn(gen, G * n, k)
     a2, b2 = _randn(gen, T, r), _randn(gen, G * n, r)
-    gather = torch.randint(0, T, [P], generator=gen, dtype=torch.int32).cuda()
-    h = torch.relu(_randn(gen, P, n))
+    gather = _dev(torch.randint(0, T, [P], generator=gen, dtype=torch.int32))
+    h = _dev(torch.relu(_randn(gen, P, n)))
     off = _offsets(GG_SIZES)
 
     def call():
@@ -246,8 +253,7 @@ def _wgrad(dtype, gathers):
         scale = torch.rand([P], generator=gen) + 0.5
         want, want_bias = ref_wgrad(grad.double(), a.double(), [0] + list(np.cumsum(sizes)), view, gg, ga,
                                     scale, size)
-        cuda = lambda t: None if t is None else t.cuda()         # noqa: E731
-        args = [cuda(t) for t in (grad, a, gg, ga, scale)]
+        args = [None if t is None else _dev(t) for t in (grad, a, gg, ga, scale)]
         off = _offsets(sizes)
 
         def call():
@@ -282,7 +288,7 @@ def _split_bf16():
     def check(outs):
         blocks = (cols + 31) // 32
         raw = outs[0].view(torch.bfloat16).view(rows, blocks, 2, 32)
-        pad = torch.zeros([rows, blocks * 32], device='cuda')
+        pad = _dev(torch.zeros([rows, blocks * 32]))
         pad[:, :cols] = x
         hi = pad.bfloat16()
         lo = (pad - hi.float()).bfloat16()
@@ -403,10 +409,10 @@ def _lora_down_stacked():
     gen = _gen(10)
     G, rows, K = 3, 333, 64
     xs, stack = _randn(gen, G, rows, K), _randn(gen, G, K, 16)
-    off = torch.arange(0, G * rows + 1, rows, dtype=torch.int32).cuda()
+    off = _dev(torch.arange(0, G * rows + 1, rows, dtype=torch.int32))
 
     def call():
-        out = torch.empty([rows, 16 * G], device='cuda')
+        out = torch.empty([rows, 16 * G], device=xs.device)
         return ext.lora_down_stacked(list(xs.unbind(0)), list(stack.unbind(0)), off, out)
 
     def check(outs):
@@ -469,7 +475,7 @@ def _route_prob(gen):
     prob = torch.rand([R_T, R_G], generator=gen) * 0.5
     prob[:, 3] += 0.6
     prob[:, 5] += 0.55
-    return prob.cuda()
+    return _dev(prob)
 
 
 def _check_routing(prob, token, block, offsets, pos):
@@ -477,7 +483,7 @@ def _check_routing(prob, token, block, offsets, pos):
     assert block.tolist() == [3] * R_T + [5] * R_T
     assert sorted(token[:R_T].tolist()) == list(range(R_T)) and sorted(token[R_T:].tolist()) == list(range(R_T))
     p = pos.long()
-    assert (token[p] == torch.arange(R_T, device='cuda')[:, None]).all()
+    assert (token[p] == _dev(torch.arange(R_T))[:, None]).all()
 
 
 def _route_topk():
@@ -511,8 +517,8 @@ def _route_topk_logits():
     from naive_gpt import ext
     gen = _gen(15)
     prob = _route_prob(gen).clamp(1e-3, 1 - 1e-3)
-    bias = (torch.rand([R_G], generator=gen) * 0.01).cuda()
-    logits = torch.zeros([R_T, 16], device='cuda')
+    bias = _dev(torch.rand([R_G], generator=gen) * 0.01)
+    logits = _dev(torch.zeros([R_T, 16]))
     logits[:, :R_G] = torch.log(prob / (1 - prob)) - bias
 
     def call():
@@ -533,13 +539,13 @@ def _route_coeff_backward(with_prob):
         prob = _route_prob(gen)
         token, block, offsets, pos = ext.route_topk(prob, R_K)
         dcoeff = _randn(gen, R_T * R_K)
-        sig = torch.sigmoid(prob)
+        sig = _dev(torch.sigmoid(prob))
 
         def call():
             return ext.route_coeff_backward(dcoeff, pos, block, R_SCALE, R_G, prob=sig if with_prob else None)
 
         def check(outs):
-            want = torch.zeros([R_T, R_G], dtype=torch.float64, device='cuda')
+            want = _dev(torch.zeros([R_T, R_G], dtype=torch.float64))
             want[token.long(), block.long()] = R_SCALE * dcoeff.double()
             if with_prob:
                 want = want * sig.double() * (1 - sig.double())
@@ -555,8 +561,8 @@ def _ffn_coeff_grad():
     P, T, r, w = 301, 200, 16, 3
     dm, da, du, z = _randn(gen, P, w), _randn(gen, P, w), _randn(gen, P, r), _randn(gen, P, r)
     u, dzt = _randn(gen, T, r), _randn(gen, T, r)
-    token = torch.randint(0, T, [P], generator=gen, dtype=torch.int32).cuda()
-    coeff = torch.rand([P], generator=gen).cuda()
+    token = _dev(torch.randint(0, T, [P], generator=gen, dtype=torch.int32))
+    coeff = _dev(torch.rand([P], generator=gen))
 
     def call():
         return ext.ffn_coeff_grad(dm, da, du, u, dzt, z, token, coeff, 0.25)
@@ -579,7 +585,7 @@ def _rows_combine(form):
         T, k, d, ns = 257, 2, 100, 16
         dt = torch.bfloat16 if form == 'bf16' else torch.float32
         rows, bias = _randn(gen, T * k + 3, d, dtype=dt), _randn(gen, d, dtype=dt)
-        pos = torch.randperm(T * k, generator=gen).int().view(T, k).cuda()
+        pos = _dev(torch.randperm(T * k, generator=gen).int().view(T, k))
         side, sw = _randn(gen, T, ns), _randn(gen, ns, d)
 
         def call():
@@ -633,16 +639,16 @@ def _embedding_rows_backward():
     from naive_gpt import ext
     gen = _gen(20)
     rows, T, width = 50, 40, 24
-    ids = torch.tensor([3, 7, 11, 49])[torch.randint(0, 4, [T], generator=gen)].cuda()
+    ids = _dev(torch.tensor([3, 7, 11, 49])[torch.randint(0, 4, [T], generator=gen)])
     g = _randn(gen, T, width)
 
     def call():
         return ext.embedding_rows_backward(g, ids, rows)
 
     def check(outs):
-        want = torch.zeros([rows, width], dtype=torch.float64, device='cuda').index_add_(0, ids, g.double())
+        want = _dev(torch.zeros([rows, width], dtype=torch.float64)).index_add_(0, ids, g.double())
         _close(outs[0], want, 'grad', rtol=1e-6)
-        absent = torch.ones(rows, dtype=torch.bool, device='cuda')
+        absent = _dev(torch.ones(rows, dtype=torch.bool))
         absent[ids] = False
         _zero_rows(outs[0], absent, 'rows no id names')
     return call, check
@@ -652,15 +658,15 @@ def _cross_entropy():
     from naive_gpt import ext
     gen = _gen(21)
     rows, V, ld = 33, 1001, 1008                  # V not a multiple of the block, pad columns
-    z = (3.0 * torch.randn([rows, V], generator=gen)).cuda()
-    target = torch.randint(0, V, [rows], generator=gen).cuda()
+    z = _dev(3.0 * torch.randn([rows, V], generator=gen))
+    target = _dev(torch.randint(0, V, [rows], generator=gen))
     target[::4] = -100
-    buf0 = torch.full([rows, ld], 7.0, device='cuda')
+    buf0 = _dev(torch.full([rows, ld], 7.0))
     buf0[:, :V] = z
-    scale = (1.0 / (target != -100).sum().float()).reshape(1)
+    scale = _dev((1.0 / (target != -100).sum().float()).reshape(1))
 
     def call():
-        buf = buf0.clone()
+        buf = _dev(buf0.clone())            # the entry works in place: its output is this operand
         loss = ext.cross_entropy_grad_(buf, V, target, scale)
         return loss, buf
 
@@ -676,11 +682,11 @@ def _cross_entropy():
     return call, check
 
 
-def _layernorm(rows, rms):
+def _layernorm(rows, rms, width=None):
     def build():
         from naive_gpt import ext
         gen = _gen(22 + rows)
-        d = min(ext.LAYERNORM_WIDTHS)
+        d = min(ext.LAYERNORM_WIDTHS) if width is None else width
         x, r, dy, dskip = (_randn(gen, rows, d) for _ in range(4))
         gamma = _randn(gen, d)
         beta = None if rms else _randn(gen, d)
@@ -716,9 +722,9 @@ def _rotary(transpose):
         from naive_gpt import ext, layers
         gen = _gen(23)
         N, S, H, E = 1, 130, 3, 64
-        emb = layers.RotaryEmbedding(n_embeddings=256, d_model=E).cuda()
+        emb = layers.RotaryEmbedding(n_embeddings=256, d_model=E)._apply(_dev)      # its tables, as Module.cuda moves them
         xs = [_randn(gen, N, S, H, E) for _ in range(3)]
-        ids = torch.arange(S, device='cuda')
+        ids = _dev(torch.arange(S))
 
         def call():
             return ext.rotary(xs, 2, emb.cos_cached, emb.sin_cached, transpose=transpose)
@@ -752,7 +758,7 @@ def _cdist():
     q, t = torch.randn([M, NQ, D], generator=gen), torch.randn([M, C, D], generator=gen)
     go = torch.randn([M, NQ, C], generator=gen)
     go[:, :, 5:9] = 0                       # centroids whose distances get no gradient
-    qd, td, god = q.cuda(), t.cuda(), go.cuda()
+    qd, td, god = _dev(q), _dev(t), _dev(go)
 
     def call():
         d, i = ext.cdist_forward_cuda(qd, td)
@@ -797,9 +803,9 @@ def _pq(which):
         z = torch.randn([N, S, H, E], generator=gen)
         k2 = torch.randn([N, S, H, E], generator=gen)
         table = torch.randn([M, C, D], generator=gen)
-        zd, td = z.cuda(), table.cuda()
-        pair = torch.stack([z, k2]).cuda()
-        upstream = torch.ones([], device='cuda')
+        zd, td = _dev(z), _dev(table)
+        pair = _dev(torch.stack([z, k2]))
+        upstream = _dev(torch.ones([]))
         assert ext.pq_loss_supported(zd, td)
 
         def call():
@@ -810,7 +816,7 @@ def _pq(which):
                 gz, gt = ext.pq_loss_backward(zd, td, upstream)
                 return loss, codes, gz, gt
             loss, cq, ck = ext.pq_loss_forward_pair(pair[0], pair[1], td)
-            both = torch.zeros([2, *z.shape], device='cuda')
+            both = _dev(torch.zeros([2, *z.shape]))
             gt = ext.pq_loss_backward_pair(pair[0], pair[1], td, upstream, both[0], both[1])
             return loss, cq, ck, both, gt
 
@@ -847,7 +853,7 @@ def _lookup():
     q = torch.randint(0, 3, [B, S, M], generator=gen, dtype=torch.int32)
     k = torch.randint(0, 3, [B, S, M], generator=gen, dtype=torch.int32)
     config = torch.empty([coeff], device='cpu')
-    qd, kd = q.cuda(), k.cuda()
+    qd, kd = _dev(q), _dev(k)
 
     def call():
         return ext.lookup_forward_cuda(config, qd, kd)
@@ -878,7 +884,7 @@ def _sddmm():
     from naive_gpt import ext
     from oracle import ext_stub
     indptr, idx, q, k, _ = _csr_inputs(27)
-    d = [t.cuda() for t in (indptr, idx, q, k)]
+    d = [_dev(t) for t in (indptr, idx, q, k)]
 
     def call():
         return ext.sddmm_forward_cuda(False, True, *d, scale=0.5, clamp=3.0)
@@ -902,7 +908,7 @@ def _spmm(trans, mfma):
             x, vals = torch.randn([2, 256, 64], generator=gen), torch.randn([2, idx.size(1)], generator=gen)
         else:
             indptr, idx, _, x, vals = _csr_inputs(28 + trans)
-        d = [t.cuda() for t in (indptr, idx, vals, x)]
+        d = [_dev(t) for t in (indptr, idx, vals, x)]
 
         def call():
             with _env('SPT_SPMM_MFMA', '1' if mfma else '0'):
@@ -913,7 +919,7 @@ def _spmm(trans, mfma):
                                               indptr, idx, vals, x)
             _close(outs[0], want, 'y', rtol=1e-5)
             if not trans and not mfma:
-                empty = (indptr[1:] == indptr[:-1]).cuda()
+                empty = _dev(indptr[1:] == indptr[:-1])
                 assert empty.any()
                 assert (outs[0][:, empty] == 0).all(), 'empty rows not exactly 0'
         return call, check
@@ -925,7 +931,7 @@ def _spmm_transposed(memo):
         from naive_gpt import ext
         from oracle import ext_stub
         indptr, idx, _, x, vals = _csr_inputs(30)
-        d_indptr, d_idx, d_vals, d_x = [t.cuda() for t in (indptr, idx, vals, x)]
+        d_indptr, d_idx, d_vals, d_x = [_dev(t) for t in (indptr, idx, vals, x)]
 
         def call():
             t = ext.transposed_for(d_indptr, d_idx) if memo else ext.csr_transpose(d_indptr, d_idx)
@@ -949,7 +955,7 @@ def _softmax(which):
         y = ext_stub.softmax_forward_cuda(indptr, idx, vals)
         raw = vals * 4.0
         scores = (raw * np.float32(0.5)).clamp(-1.0, 1.0)
-        d = lambda t: t.cuda()                       # noqa: E731
+        d = _dev
 
         def call():
             if which == 'fwd':
@@ -993,6 +999,14 @@ def _dead_key_indices(B, S, Z, gen, distinct=False):
     return idx.view(B, S * Z)
 
 
+def _once(memo, make):
+    """make(), computed by the first build of a case and shared by its later ones: the inputs come
+    from the case's seed, so every build would compute the same reference."""
+    if 'value' not in memo:
+        memo['value'] = make()
+    return memo['value']
+
+
 def _attn_refs(idx, q, k, v, gy, scale):
     from oracle import ext_stub
     from test_gpu_fused_attention import oracle_chain
@@ -1012,6 +1026,8 @@ def _attn_refs(idx, q, k, v, gy, scale):
 
 
 def _mfma(N, H, S, Z, E, gt, builder=None, bf16=False):
+    memo = {}
+
     def build():
         from naive_gpt import ext
         gen = _gen(S + Z + E)
@@ -1024,10 +1040,10 @@ def _mfma(N, H, S, Z, E, gt, builder=None, bf16=False):
         idx = _dead_key_indices(B, S, Z, gen, distinct=builder is not None)
         scale = E ** -0.5
         dt = torch.bfloat16 if bf16 else torch.float32
-        qd, kd, vd = (t.to(dt).cuda() for t in (q, k, v))
-        idd = idx.cuda()
-        gyd = (gy.transpose(1, 2).contiguous() if gt else gy).to(dt).cuda()
-        refs = _attn_refs(idx, q, k, v, gy, scale)
+        qd, kd, vd = (_dev(t.to(dt)) for t in (q, k, v))
+        idd = _dev(idx)
+        gyd = _dev((gy.transpose(1, 2).contiguous() if gt else gy).to(dt))
+        refs = _once(memo, lambda: _attn_refs(idx, q, k, v, gy, scale))
 
         layout = {}
 
@@ -1057,6 +1073,8 @@ def _mfma(N, H, S, Z, E, gt, builder=None, bf16=False):
 
 
 def _fused_attention(S, yt, causal):
+    memo = {}
+
     def build():
         from naive_gpt import ext
         from test_gpu_fused_attention import causal_indices
@@ -1067,9 +1085,9 @@ def _fused_attention(S, yt, causal):
         gy = torch.randn([B, S, E], generator=gen)
         idx = causal_indices(B, S, Z, gen)
         scale = E ** -0.5
-        refs = _attn_refs(idx, q, k, v, gy, scale)
-        qd, kd, vd, idd = q.cuda(), k.cuda(), v.cuda(), idx.cuda()
-        gyd = (gy.transpose(1, 2).contiguous() if yt else gy).cuda()
+        refs = _once(memo, lambda: _attn_refs(idx, q, k, v, gy, scale))
+        qd, kd, vd, idd = _dev(q), _dev(k), _dev(v), _dev(idx)
+        gyd = _dev(gy.transpose(1, 2).contiguous() if yt else gy)
         assert ext.fused_attention_supported(S, E, B, S * Z)
 
         def call():
@@ -1245,13 +1263,13 @@ def _sites(paths, site):
     return {k[1] for k in paths if k[0] == site}
 
 
-@pytest.mark.parametrize('kind', ['opt', 'llama'])
-def test_model_step_ignores_what_its_buffers_held(kind):
-    """Loss and every parameter gradient of one SparseTuner step of an upgraded model on the default
-    fused paths: matrix-core attention, fused routed FFN, fused norm, fused head loss, LoRA kernels.
-    The attention backward sums grad_k / grad_v with float atomics (DET above does not hold for
-    it), so outputs that differ in bits from the `zero` run are held to 1e-5 of scale instead; the
-    layer-level tests below, which have no atomic path, require the same bits."""
+STEP_PATHS = (('attention', 'mfma'), ('routed_ffn', 'fused'), ('route_topk', 'kernel'), ('norm', 'kernel'),
+              ('head_loss', 'fused'))
+
+
+def model_step(kind):
+    """(run, tuner) for the upgraded `kind` model of STEP_CONFIG on a STEP_BATCH batch: run() is one
+    SparseTuner step -> [loss, every parameter gradient]; release the tuner when done."""
     from naive_gpt import utils
     from naive_gpt.utils import checkpoint
     torch.manual_seed(0)
@@ -1271,14 +1289,23 @@ def test_model_step_ignores_what_its_buffers_held(kind):
         loss = loss + tuner.aux_weight * tuner.aux_loss()
         loss.backward()
         return [loss] + [p.grad for _, p in model.named_parameters() if p.grad is not None]
+    return run, tuner
 
+
+@pytest.mark.parametrize('kind', ['opt', 'llama'])
+def test_model_step_ignores_what_its_buffers_held(kind):
+    """Loss and every parameter gradient of one SparseTuner step of an upgraded model on the default
+    fused paths: matrix-core attention, fused routed FFN, fused norm, fused head loss, LoRA kernels.
+    The attention backward sums grad_k / grad_v with float atomics (DET above does not hold for
+    it), so outputs that differ in bits from the `zero` run are held to 1e-5 of scale instead; the
+    layer-level tests below, which have no atomic path, require the same bits."""
+    run, tuner = model_step(kind)
     try:
         runs = _poisoned_runs(run)
     finally:
         tuner.release()
     base, paths = runs['zero']
-    for site, want in (('attention', 'mfma'), ('routed_ffn', 'fused'), ('route_topk', 'kernel'),
-                       ('norm', 'kernel'), ('head_loss', 'fused')):
+    for site, want in STEP_PATHS:
         assert _sites(paths, site) == {want}, (site, sorted(paths))
     assert len(base) > 10
     for pattern in PATTERNS[1:]:

@@ -41,6 +41,40 @@ def test_every_launching_entry_has_a_poison_case():
     assert all(c.kind in (suite.DET, suite.ATOMIC) for cases in suite.CASES.values() for c in cases)
 
 
+def test_every_case_operand_reaches_the_device_through_dev():
+    """No function defined above `CASES` in test_gpu_poisoned_buffers.py, nested ones included, calls
+    `.cuda(` or passes `device='cuda'`, except `_dev` itself: test_gpu_guard_bands swaps `_dev` for
+    guard.home, and an operand moved any other way would lie outside the guard bands."""
+    source = open(suite.__file__).read()
+    tree = ast.parse(source)
+    cases_line = next(n.lineno for n in tree.body if isinstance(n, ast.Assign)
+                      and any(isinstance(t, ast.Name) and t.id == 'CASES' for t in n.targets))
+    funcs = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.lineno < cases_line]
+    assert len(funcs) > 40 and any(f.name == '_dev' for f in funcs)
+    direct = []
+    for f in funcs:
+        if f.name == '_dev':
+            assert any(isinstance(c, ast.Call) and isinstance(c.func, ast.Attribute) and c.func.attr == 'cuda'
+                       for c in ast.walk(f)), '_dev no longer moves its argument itself'
+            continue
+        for c in ast.walk(f):
+            if not isinstance(c, ast.Call):
+                continue
+            if isinstance(c.func, ast.Attribute) and c.func.attr == 'cuda':
+                direct.append('{}:{} .cuda()'.format(f.name, c.lineno))
+            for k in c.keywords:
+                if k.arg == 'device' and not (isinstance(k.value, ast.Constant) and k.value.value in ('cpu', 'meta')) \
+                        and 'cuda' in ast.unparse(k.value):
+                    direct.append('{}:{} device={}'.format(f.name, c.lineno, ast.unparse(k.value)))
+            if any(isinstance(a, ast.Constant) and a.value == 'cuda' for a in c.args):       # .to('cuda') and kin
+                direct.append('{}:{} \'cuda\' as an argument'.format(f.name, c.lineno))
+    assert not direct, 'operands that bypass _dev: {}'.format(direct)
+    # the same in the text, comments and strings aside: the AST walk above and this agree
+    above = source[:source.index('\nCASES = {')]
+    lines = [l for l in above.split('\n') if ('.cuda(' in l or "device='cuda'" in l) and 'return t.cuda()' not in l]
+    assert not lines, lines
+
+
 def test_uint8_workspaces_are_classified():
     """Each `torch.empty([...], dtype=torch.uint8` of ext.py sits in a function that tests/poison.py
     classifies as float-only or as holding indices / counters."""

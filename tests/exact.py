@@ -148,3 +148,53 @@ def fp32_sum_bound(mag: torch.Tensor, n: int) -> torch.Tensor:
     u = 2.0 ** -24
     return (n + 1) * u / (1 - (n + 1) * u) * mag
 
+
+
+def fp32_tree_bound(mag: torch.Tensor, depth) -> torch.Tensor:
+    """Error of an fp32 sum in which every term passes through at most `depth` roundings (additions or
+    fmas on its way to the result, its own product's rounding counted as one): gamma_depth * mag, `mag`
+    the sum of the terms' magnitudes.  The caller states the depth from the kernel's summation
+    structure (serial steps per lane, levels of the butterfly, partial sums); fp32_sum_bound is the
+    any-order form, for short serial chains.  `depth`: an int, or a tensor that broadcasts against `mag`
+    (rows of different lengths)."""
+    assert float(torch.as_tensor(depth).min()) >= 0
+    u = 2.0 ** -24
+    return depth * u / (1 - depth * u) * mag
+
+
+def eval_bound(value: torch.Tensor, ulps: float, arg=None) -> torch.Tensor:
+    """Error of one device function evaluation: `ulps` u |value|, plus |arg| u |value| when the function
+    is an exponential that scales its argument first (__expf(x) = v_exp_f32(x log2e): the product's
+    rounding moves the result by |x| u relative)."""
+    u = 2.0 ** -24
+    out = ulps * u * value.abs()
+    if arg is not None:
+        out = out + arg.abs() * u * value.abs()
+    return out
+
+
+def assert_within(got: torch.Tensor, ref64: torch.Tensor, bound: torch.Tensor, what: str) -> float:
+    """|got - ref64| <= bound for every element (exact equality where bound == 0).  Prints one
+    `[contract]` line (worst ratio err / bound; share of elements below 1e-3 max|ref|), fails naming the
+    worst element, returns the worst ratio."""
+    assert ref64.dtype == torch.float64 and got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    got = got.detach().double().cpu().reshape(-1)
+    ref = ref64.detach().cpu().reshape(-1)
+    bound = torch.as_tensor(bound, dtype=torch.float64).cpu()
+    bound = bound.expand(ref64.shape).reshape(-1) if bound.dim() else bound.expand_as(ref)
+    assert ref.numel() > 0 and torch.isfinite(ref).all() and (bound >= 0).all(), what
+    err = (got - ref).abs()
+    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float('inf')))
+    zero = bound == 0
+    ratio = torch.where(zero, torch.where(err == 0, 0.0, float('inf')).double(), err / bound.clamp_min(1e-300))
+    worst = float(ratio.max())
+    share = float((ref.abs() < 1e-3 * ref.abs().max()).double().mean())
+    print('[contract] {}: worst ratio {:.3f}, share of elements below 1e-3 max|ref| {:.1%}'.format(
+        what, worst, share))
+    if not worst <= 1.0:
+        i = int(ratio.argmax())
+        raise AssertionError('{}: element {} of {} is off its bound: got {!r}, reference {!r}, |err| {:.3e}, '
+                             'bound {:.3e} (ratio {:.3f}); {} elements off'.format(
+                                 what, i, ref.numel(), got[i].item(), ref[i].item(), err[i].item(),
+                                 bound[i].item(), worst, int((ratio > 1).sum())))
+    return worst

@@ -62,9 +62,9 @@ def matrix_core_entries():
     return sorted(e for e in launching_entries() if 'bf16' in e or e in ELSEWHERE or reaches(e))
 
 
-def called_by_tiers():
+def called_by_tiers(tiers=TIERS):
     names = set()
-    for t in TIERS:
+    for t in tiers:
         for node in ast.walk(ast.parse(open(os.path.join(HERE, t)).read())):
             if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute):
                 names.add(node.func.attr)

@@ -677,6 +677,15 @@ int spt_lora_down_tables(const float *x, long long ldx, long long rows, int k, c
 int spt_lora_down2(const float *x, long long ldx, long long rows, int k, const float *l, int n,
                    const float *l2, int n2, float *u, long long ldu, int u_block_major, void *image,
                    float *norms, int exact, void *stream);
+/* spt_lora_down2 with l2 the routed FFN's ROUTER (n2 = n_blocks <= 8 rows, n = 16): the launch also ranks
+ * logit + bias (bias [n2] or null) of its rows exactly as spt_route_topk_logits will -- the top_k largest, NaN
+ * above every number, ties to the lower block -- and writes counts[i * MG + g] = how many of rows 16 i ..
+ * 16 i + 15 (below `rows`) selected block g, 0 for g >= n2; MG = 4 for n2 <= 4, else 8; counts int32
+ * [ceil(rows / 16), MG], written whole.  spt_route_topk_counted reads it. */
+int spt_lora_down2_route(const float *x, long long ldx, long long rows, int k, const float *l, int n,
+                         const float *l2, int n2, const float *bias, int top_k, int32_t *counts, float *u,
+                         long long ldu, int u_block_major, void *image, float *norms, int exact,
+                         void *stream);
 /*
  * The per-block tables of the routed FFN (lora_ffn.py:87-111: `h_i @ l2[i]`, and `ds_i @ r1[i]` in
  * its backward): rows offsets[g] .. offsets[g + 1] - 1 (device int32 [n_groups + 1], rows sorted by
@@ -837,6 +846,13 @@ int spt_route_topk_logits(const float *logits, int ld, const float *bias, float 
                           int32_t *block, int32_t *offsets, int32_t *pos, long long *token64,
                           long long *block64, float *coeff, float scale, int n_tokens, int n_blocks,
                           int k, void *stream);
+/* spt_route_topk_logits with the per-group selection counts of spt_lora_down2_route (same logits, bias,
+ * n_blocks and k): every workgroup sums the counts in front of its 256 tokens instead of ranking all tokens
+ * again.  Outputs bit for bit those of spt_route_topk_logits. */
+int spt_route_topk_counted(const float *logits, int ld, const float *bias, const int32_t *counts, float *prob,
+                           int32_t *token, int32_t *block, int32_t *offsets, int32_t *pos,
+                           long long *token64, long long *block64, float *coeff, float scale, int n_tokens,
+                           int n_blocks, int k, void *stream);
 int spt_route_coeff_backward(const float *dcoeff, const int32_t *pos, const int32_t *block,
                              float scale, float *dprob, int n_tokens, int n_blocks, int k,
                              void *stream);
@@ -856,6 +872,20 @@ int spt_ffn_coeff_grad(const float *dot_main, const float *dot_act, int width, c
                        const float *u, const float *dzt, const float *z, const int32_t *token,
                        const float *coeff, float floor_value, float *out, int n_rows, int rank,
                        void *stream);
+/*
+ * The router's share of that backward in one launch: spt_ffn_coeff_grad, spt_rows_combine of du and of z
+ * over pos, and spt_route_logit_backward, each output bit for bit what those four calls give:
+ *   dlogit [n_tokens, n_blocks], du_tok = sum_j du[pos[t, j]] and z_tok = sum_j z[pos[t, j]] [n_tokens, rank];
+ *   dcoeff [n_tokens * k] (the per-row coefficient gradient) only when not null.
+ * pos [n_tokens, k], block [n_tokens * k] as spt_route_topk_logits leaves them; prob [n_tokens, n_blocks]
+ * the sigmoid's outputs; coeff [n_tokens * k].  rank == 16, n_blocks <= 8 (SPT_EUNSUP otherwise); the
+ * [*, rank] operands 16-byte aligned.
+ */
+int spt_ffn_router_backward(const float *dot_main, const float *dot_act, int width, const float *du,
+                            const float *u, const float *dzt, const float *z, const int32_t *pos,
+                            const int32_t *block, const float *coeff, float floor_value, float scale,
+                            const float *prob, float *dlogit, float *du_tok, float *z_tok, float *dcoeff,
+                            int n_tokens, int n_blocks, int k, int rank, void *stream);
 
 /*
  * Rotary position embedding (position.py:24-34: y = cos[s] * x + sin[s] * rotate_half(x)) of up to

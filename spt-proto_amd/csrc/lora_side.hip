@@ -34,6 +34,7 @@
 // The split image (hi / lo bf16 of x) is written by the same pass in both forms.
 #include "split_bf16.h"
 #include "norm_apply.h"
+#include "route_rank.h"
 #include <type_traits>
 
 namespace spt {
@@ -66,12 +67,18 @@ constexpr int LS_NW = 8;            // waves per workgroup = shares of K (8192 r
 // sparse/feedforward.py:22-25, riding the pass that forms x . L1); columns n2 .. 15 of that block are 0.
 // (L2 is a template parameter: as a run-time branch in the table loads it took the single-table
 // kernel from 98 to 230 registers and from 11 to 20 us)
-template <int NB, bool IMAGE, bool NORMS, bool EXACT, bool L2 = false>
+// Selection counts (ROUTE = 4 or 8 block slots, with L2; spt_lora_down2_route): the workgroup owns 16 whole rows
+// and ends with their final logits, so it ranks logit + bias itself (route_rank.h: the ranking of
+// route_topk_kernel, on the bits it will read) and writes counts[blockIdx.x][g] = how many of its rows
+// t < rows selected block g (0 for g >= r_blocks).  The routing launch then sums 8 KiB of integers instead
+// of re-ranking every token in every workgroup.  A template parameter for the reason L2 is one.
+template <int NB, bool IMAGE, bool NORMS, bool EXACT, bool L2 = false, int ROUTE = 0>
 __global__ __launch_bounds__(64 * LS_NW) void lora_down_kernel(
     const float *__restrict__ x, long long ldx, long long rows, int K, const float *__restrict__ l,
     int n, float *__restrict__ u, long long u_ld, long long u_block, char *__restrict__ image,
     float *__restrict__ norms, const int32_t *__restrict__ offsets, int n_groups, long long l_gstride,
-    const float *__restrict__ l2, int n2, long long l_bstride, int group_cols) {
+    const float *__restrict__ l2, int n2, long long l_bstride, int group_cols,
+    const float *__restrict__ r_bias, int r_blocks, int r_k, int32_t *__restrict__ counts) {
     // (group_cols, grouped form: row r of group q is stored at u[(r - offsets[q]) * u_ld + q * n + c]
     // -- equal groups side by side as column blocks of ONE matrix: dU_q | dU_k | dU_v of a joint
     // projection's backward from one launch over [dQ; dK; dV])
@@ -80,6 +87,7 @@ __global__ __launch_bounds__(64 * LS_NW) void lora_down_kernel(
     // in a tuner's flat parameter buffer: no concatenated copy of them is made)
     __shared__ float red[LS_NW][NB][256];
     __shared__ float nred[LS_NW][16];
+    __shared__ float logit[ROUTE ? 16 : 1][ROUTE ? ROUTE : 1];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
@@ -204,6 +212,22 @@ __global__ __launch_bounds__(64 * LS_NW) void lora_down_kernel(
         for (int q = 0; q < LS_NW; q += 2) v += red[q][b][e] + red[q + 1][b][e];
         const long long orow = row0 + 4 * (ln >> 4) + j;
         if (orow < rows) u[b * u_block + orow * u_ld + (ln & 15)] = v;
+        if (ROUTE && b == NB - 1 && (ln & 15) < ROUTE) logit[4 * (ln >> 4) + j][ln & 15] = v;
+    }
+    if constexpr (ROUTE != 0) {
+        __syncthreads();
+        if (w == 0) {                                        // lane r < 16 ranks row row0 + r
+            float v[ROUTE];
+#pragma unroll
+            for (int j = 0; j < ROUTE; j++)
+                v[j] = j < r_blocks ? logit[lane & 15][j] + (r_bias ? r_bias[j] : 0.0f) : 0.0f;
+            const unsigned m = (lane < 16 && row0 + lane < rows) ? select_topk(v, r_blocks, r_k) : 0u;
+#pragma unroll
+            for (int j = 0; j < ROUTE; j++) {
+                const int cnt_j = __popcll(__ballot((m >> j) & 1u));
+                if (lane == 0) counts[(size_t)blockIdx.x * ROUTE + j] = cnt_j;
+            }
+        }
     }
     if (NORMS && threadIdx.x < 16 && row0 + threadIdx.x < rows)
         norms[row0 + threadIdx.x] = sqrtf(((nred[0][threadIdx.x] + nred[1][threadIdx.x]) +
@@ -222,7 +246,8 @@ static int lora_down_any(const float *x, long long ldx, long long rows, int k, c
                          int n, float *u, long long ldu, int u_block_major, void *image,
                          float *norms, int exact, const int32_t *offsets, int n_groups,
                          long long l_gstride, void *stream, const float *l2 = nullptr, int n2 = 0,
-                         long long table_stride = 0, int group_cols = 0) {
+                         long long table_stride = 0, int group_cols = 0, const float *r_bias = nullptr,
+                         int r_k = 0, int32_t *counts = nullptr) {
     if (!x || !l || !u) return SPT_EINVAL;
     if (rows <= 0 || k <= 0 || n <= 0 || ldx < k) return SPT_EINVAL;
     if (l2 && (n2 <= 0 || n2 > 16 || offsets || (reinterpret_cast<uintptr_t>(l2) & 15) != 0)) return SPT_EINVAL;
@@ -241,16 +266,23 @@ static int lora_down_any(const float *x, long long ldx, long long rows, int k, c
     // u [rows, n], or (u_block_major) n / 16 contiguous matrices [rows, 16]: one per adapter
     if (ldu != 0 && (ldu < n || u_block_major)) return SPT_EINVAL;
     const long long u_ld = u_block_major ? 16 : (ldu ? ldu : n), u_block = u_block_major ? rows * 16 : 16;
-#define SPT_LD5(NB, IM, NO, EX, L2)                                                              \
-    hipLaunchKernelGGL((lora_down_kernel<NB, IM, NO, EX, L2>), dim3((unsigned)nblk), dim3(64 * LS_NW), 0, s, \
+#define SPT_LD6(NB, IM, NO, EX, L2, RT)                                                          \
+    hipLaunchKernelGGL((lora_down_kernel<NB, IM, NO, EX, L2, RT>), dim3((unsigned)nblk), dim3(64 * LS_NW), 0, s, \
                        x, ldx, rows, k, l, n_l, u, u_ld, u_block, img, norms, offsets, n_groups, l_gstride, \
-                       l2, n2, l_bstride, group_cols)
+                       l2, n2, l_bstride, group_cols, r_bias, n2, r_k, counts)
+#define SPT_LD5(NB, IM, NO, EX, L2) SPT_LD6(NB, IM, NO, EX, L2, 0)
     // (a second table only in the exact form and behind at least one block of the first table: the
     // routed FFN's router riding x . L1)
     if (l2 && (!exact || n < 32)) return SPT_EUNSUP;
+    // (selection counts: the router beside ONE rank-16 table, <= 8 blocks, every column of l2 a block)
+    if (counts && (!l2 || r_k <= 0 || r_k > n2)) return SPT_EINVAL;
+    if (counts && (n != 32 || n2 > RT_MAXG)) return SPT_EUNSUP;
 #define SPT_LD(NB, IM, NO)                                              \
     do {                                                                \
-        if (l2) { if constexpr (NB >= 2) SPT_LD5(NB, IM, NO, true, true); } \
+        if (counts) {                                                   \
+            if constexpr (NB == 2) { if (n2 <= 4) SPT_LD6(NB, IM, NO, true, true, 4); \
+                                     else SPT_LD6(NB, IM, NO, true, true, RT_MAXG); } \
+        } else if (l2) { if constexpr (NB >= 2) SPT_LD5(NB, IM, NO, true, true); } \
         else if (exact) SPT_LD5(NB, IM, NO, true, false);               \
         else SPT_LD5(NB, IM, NO, false, false);                         \
     } while (0)
@@ -270,6 +302,7 @@ static int lora_down_any(const float *x, long long ldx, long long rows, int k, c
 #undef SPT_LD_NB
 #undef SPT_LD
 #undef SPT_LD5
+#undef SPT_LD6
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }
@@ -287,6 +320,15 @@ extern "C" int spt_lora_down2(const float *x, long long ldx, long long rows, int
     if (!l2) return SPT_EINVAL;
     return lora_down_any(x, ldx, rows, k, l, n + 16, u, ldu, u_block_major, image, norms, exact, nullptr, 1,
                          0, stream, l2, n2);
+}
+
+extern "C" int spt_lora_down2_route(const float *x, long long ldx, long long rows, int k, const float *l,
+                                    int n, const float *l2, int n2, const float *bias, int top_k,
+                                    int32_t *counts, float *u, long long ldu, int u_block_major, void *image,
+                                    float *norms, int exact, void *stream) {
+    if (!l2 || !counts) return SPT_EINVAL;
+    return lora_down_any(x, ldx, rows, k, l, n + 16, u, ldu, u_block_major, image, norms, exact, nullptr, 1,
+                         0, stream, l2, n2, 0, 0, bias, top_k, counts);
 }
 
 extern "C" int spt_lora_down_grouped_cols(const float *x, long long ldx, long long rows, int k,

@@ -17,39 +17,12 @@
 // ties to the lower block index (a total order; torch.topk leaves ties unspecified).  G <= 8, T <= 65536 (64 tokens per thread); bigger
 // problems use the torch composition (layers/sparse/grouped.py).
 #include "spt_common.h"
+#include "route_rank.h"
 #include <initializer_list>
 
 namespace spt {
 
-constexpr int RT_MAXG = 8;
-
-// Orderable key of a probability: ascending unsigned order == ascending float order, -0 == +0,
-// and every NaN is the LARGEST key (torch.topk also ranks NaN above every number).  The rank
-// below is then a total order for any input, so exactly k bits are set per token: with the
-// float comparisons used before, a NaN compared false against everything, ranked 0 and let
-// a token select more than k blocks -- writes past the T * k rows the caller allocated.
-__device__ __forceinline__ unsigned order_key(float x) {
-    if (x != x) return 0xFFFFFFFFu;
-    const unsigned b = __float_as_uint(x + 0.0f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-template <int MG>
-__device__ __forceinline__ unsigned select_topk(const float (&v)[MG], int G, int k) {
-    unsigned key[MG];
-#pragma unroll
-    for (int j = 0; j < MG; j++) key[j] = order_key(v[j]);
-    unsigned mask = 0u;
-#pragma unroll
-    for (int j = 0; j < MG; j++) {
-        int rank = 0;
-#pragma unroll
-        for (int i = 0; i < MG; i++)
-            rank += (i < G) && (key[i] > key[j] || (key[i] == key[j] && i < j));
-        if (j < G && rank < k) mask |= 1u << j;
-    }
-    return mask;
-}
+// (order_key / select_topk, the ranking: route_rank.h -- shared with lora_side.hip)
 
 // A workgroup places the selections of its own 256 tokens (a thread per token); what it needs
 // of the other tokens -- how many selections per block precede its own -- it counts itself, from
@@ -60,13 +33,19 @@ __device__ __forceinline__ unsigned select_topk(const float (&v)[MG], int G, int
 // LDS: 39 us at T = 8192 (a single CU's latency chain).
 // (MG = 4 or 8 block slots compiled in: the selection is a rank over MG x MG comparisons, and
 // it is what the redundant counting repeats.)
+// COUNTED (spt_route_topk_counted): `counts` [ceil(T / 16), MG] int32 holds, per group of RT_GROUP tokens,
+// how many of them selected each block -- left by the launch that formed the logits (spt_lora_down2_route,
+// the same ranking of the same bits).  A chunk is 16 groups, so before[] and total[] are integer sums over
+// the groups in front of the chunk and over all of them (8 KiB at T = 8192), and only the workgroup's own
+// chunk is loaded and ranked: 30.6 -> see DESIGN 8.00f.  Everything after the barrier is common.
 constexpr int RT_CHUNK = 256;
-template <int MG>
+template <int MG, bool COUNTED = false>
 __global__ __launch_bounds__(RT_CHUNK) void route_topk_kernel(
     const float *__restrict__ prob, int32_t *__restrict__ token, int32_t *__restrict__ block,
     int32_t *__restrict__ offsets, int32_t *__restrict__ pos, int T, int G, int k,
     long long *__restrict__ token64, long long *__restrict__ block64, float *__restrict__ coeff,
-    float scale, int ld, const float *__restrict__ bias, float *__restrict__ prob_out) {
+    float scale, int ld, const float *__restrict__ bias, float *__restrict__ prob_out,
+    const int32_t *__restrict__ counts) {
     // (prob_out != null: `prob` holds the router's LOGITS without bias, rows `ld` floats apart --
     // the last block of spt_lora_down2.  The selection ranks logit + bias: the sigmoid is monotone, so
     // this is the ranking of the probabilities wherever two of them differ, and where distinct logits
@@ -105,7 +84,35 @@ __global__ __launch_bounds__(RT_CHUNK) void route_topk_kernel(
     for (int g = 0; g < MG; g++) my_v[g] = 0.0f;
     const unsigned long long lower = (1ull << lane) - 1ull;
     constexpr int AHEAD = 4;                  // chunks whose loads are in flight together
-    for (int c0 = 0; c0 < nchunks; c0 += AHEAD) {
+    if constexpr (COUNTED) {
+        float v[MG];
+        load(mine, v);
+        const int ngroups = (T + RT_GROUP - 1) / RT_GROUP, gmine = mine * (RT_CHUNK / RT_GROUP);
+        for (int q = tid; q < ngroups; q += RT_CHUNK) {          // (this lane's share; summed over the wave below)
+#pragma unroll
+            for (int g = 0; g < MG; g++) {
+                const int n = counts[(size_t)q * MG + g];
+                total[g] += n;
+                if (q < gmine) before[g] += n;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < MG; g++)
+#pragma unroll
+            for (int step = 1; step < SPT_WAVE; step <<= 1) {
+                before[g] += __shfl_xor(before[g], step, SPT_WAVE);
+                total[g] += __shfl_xor(total[g], step, SPT_WAVE);
+            }
+        my_mask = (mine * RT_CHUNK + tid < T) ? select_topk(v, G, k) : 0u;
+#pragma unroll
+        for (int g = 0; g < MG; g++) {
+            my_v[g] = prob_out ? 1.0f / (1.0f + expf(-v[g])) : v[g];
+            const unsigned long long b = __ballot((my_mask >> g) & 1u);
+            own[g] = __popcll(b);
+            rank[g] = __popcll(b & lower);
+        }
+    }
+    for (int c0 = 0; !COUNTED && c0 < nchunks; c0 += AHEAD) {
         float v[AHEAD][MG];
 #pragma unroll
         for (int u = 0; u < AHEAD; u++) load(min(c0 + u, nchunks - 1), v[u]);
@@ -241,6 +248,71 @@ __global__ __launch_bounds__(256) void ffn_coeff_grad_kernel(
         d2 += (c.x * e.x + c.y * e.y) + (c.z * e.z + c.w * e.w);
     }
     out[p] = (((acc + acc2) - d1) - d2) / fmaxf(coeff[p], floor_value);
+}
+
+// The router's share of the routed LoRA FFN's backward in ONE launch (spt_ffn_router_backward) instead of four
+// on [P]- and [T, 16]-sized data: ffn_coeff_grad_kernel, rows_combine_kernel of du and of z,
+// route_coeff_backward_kernel with `prob`.  Per token t, over its k rows p = pos[t, j] in j order:
+//   dcoeff[p] as ffn_coeff_grad_kernel forms it;  dlogit[t, block[p]] = ((scale dcoeff[p]) (1 - y)) y, 0 elsewhere;
+//   du_tok[t] = 0 + du[p_0] + du[p_1] + ...;  z_tok[t] likewise.
+// Four lanes per token, a float4 of the 16-float rows each (64 contiguous bytes per row and quad).  Every
+// output keeps the expression and the order of the kernel it comes from: lane i of the quad forms the
+// 4-wide dot group i, and all four add the groups in i order; lanes 0 and 1 run the two sequential sums
+// over `w`.  rank = 16 only.
+constexpr int RB_THREADS = 128;
+__global__ __launch_bounds__(RB_THREADS) void ffn_router_backward_kernel(
+    const float *__restrict__ dot_main, const float *__restrict__ dot_act, int w,
+    const float *__restrict__ du, const float *__restrict__ u, const float *__restrict__ dzt,
+    const float *__restrict__ z, const int32_t *__restrict__ pos, const int32_t *__restrict__ block,
+    const float *__restrict__ coeff, float floor_value, float scale, const float *__restrict__ prob,
+    float *__restrict__ dlogit, float *__restrict__ du_tok, float *__restrict__ z_tok,
+    float *__restrict__ dcoeff, int T, int G, int k) {
+    const int sub = threadIdx.x & 3, quad = (threadIdx.x & 63) & ~3;
+    const int t_raw = blockIdx.x * (RB_THREADS / 4) + (threadIdx.x >> 2);
+    const bool live = t_raw < T;                     // (quad-uniform; dead quads follow token T - 1 and store nothing)
+    const int t = min(t_raw, T - 1);
+    const float4 b = *reinterpret_cast<const float4 *>(u + (size_t)t * 16 + 4 * sub);
+    const float4 c = *reinterpret_cast<const float4 *>(dzt + (size_t)t * 16 + 4 * sub);
+    float4 su = make_float4(0.f, 0.f, 0.f, 0.f), sz = make_float4(0.f, 0.f, 0.f, 0.f);
+    float out_lo = 0.0f, out_hi = 0.0f;              // d prob of blocks sub and sub + 4
+    for (int j = 0; j < k; j++) {
+        const int p = pos[(size_t)t * k + j];
+        const float4 a = *reinterpret_cast<const float4 *>(du + (size_t)p * 16 + 4 * sub);
+        const float4 e = *reinterpret_cast<const float4 *>(z + (size_t)p * 16 + 4 * sub);
+        float part = 0.0f;                           // lane 0: sum of dot_main[p, :]; lane 1: of dot_act[p, :]
+        if (sub < 2) {
+            const float *src = (sub == 0 ? dot_main : dot_act) + (size_t)p * w;
+            for (int i = 0; i < w; i++) part += src[i];
+        }
+        const float g1 = (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+        const float g2 = (c.x * e.x + c.y * e.y) + (c.z * e.z + c.w * e.w);
+        const float acc = __shfl(part, quad, SPT_WAVE), acc2 = __shfl(part, quad + 1, SPT_WAVE);
+        float d1 = 0.0f, d2 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            d1 += __shfl(g1, quad + i, SPT_WAVE);
+            d2 += __shfl(g2, quad + i, SPT_WAVE);
+        }
+        const float dc = (((acc + acc2) - d1) - d2) / fmaxf(coeff[p], floor_value);
+        if (dcoeff && live && sub == 0) dcoeff[p] = dc;
+        const int blk = block[p];
+        const float v = scale * dc;
+        if (blk == sub) out_lo = v;
+        if (blk == sub + 4) out_hi = v;
+        su.x += a.x; su.y += a.y; su.z += a.z; su.w += a.w;
+        sz.x += e.x; sz.y += e.y; sz.z += e.z; sz.w += e.w;
+    }
+    if (!live) return;
+    *reinterpret_cast<float4 *>(du_tok + (size_t)t * 16 + 4 * sub) = su;
+    *reinterpret_cast<float4 *>(z_tok + (size_t)t * 16 + 4 * sub) = sz;
+    if (sub < G) {
+        const float y = prob[(size_t)t * G + sub];
+        dlogit[(size_t)t * G + sub] = (out_lo * (1.0f - y)) * y;
+    }
+    if (sub + 4 < G) {
+        const float y = prob[(size_t)t * G + sub + 4];
+        dlogit[(size_t)t * G + sub + 4] = (out_hi * (1.0f - y)) * y;
+    }
 }
 
 // ---- the gated FFN's elementwise middle (LLaMaFeedforward: h = silu(gate) * side,
@@ -487,21 +559,21 @@ extern "C" int spt_swiglu_backward_bf16(const void *grad_h, const void *gate, co
 static int route_topk_any(const float *prob, int32_t *token, int32_t *block, int32_t *offsets,
                           int32_t *pos, long long *token64, long long *block64, float *coeff,
                           float scale, int n_tokens, int n_blocks, int k, void *stream, int ld = 0,
-                          const float *bias = nullptr, float *prob_out = nullptr) {
+                          const float *bias = nullptr, float *prob_out = nullptr,
+                          const int32_t *counts = nullptr) {
     if (!prob || !token || !block || !offsets || !pos) return SPT_EINVAL;
     if (n_tokens <= 0 || n_blocks <= 0 || k <= 0 || k > n_blocks) return SPT_EINVAL;
     if (n_blocks > RT_MAXG || n_tokens > 65536) return SPT_EUNSUP;
     if (ld == 0) ld = n_blocks;
     if (ld < n_blocks || (reinterpret_cast<uintptr_t>(prob) & 15) != 0) return SPT_ESHAPE;
     const dim3 grid((n_tokens + RT_CHUNK - 1) / RT_CHUNK), threads(RT_CHUNK);
-    if (n_blocks <= 4)
-        hipLaunchKernelGGL(route_topk_kernel<4>, grid, threads, 0, (hipStream_t)stream, prob, token,
-                           block, offsets, pos, n_tokens, n_blocks, k, token64, block64, coeff, scale,
-                           ld, bias, prob_out);
-    else
-        hipLaunchKernelGGL(route_topk_kernel<RT_MAXG>, grid, threads, 0, (hipStream_t)stream, prob, token,
-                           block, offsets, pos, n_tokens, n_blocks, k, token64, block64, coeff, scale,
-                           ld, bias, prob_out);
+#define SPT_RT(MG, COUNTED)                                                                              \
+    hipLaunchKernelGGL((route_topk_kernel<MG, COUNTED>), grid, threads, 0, (hipStream_t)stream, prob, token, \
+                       block, offsets, pos, n_tokens, n_blocks, k, token64, block64, coeff, scale, ld, bias, \
+                       prob_out, counts)
+    if (n_blocks <= 4) { if (counts) SPT_RT(4, true); else SPT_RT(4, false); }
+    else { if (counts) SPT_RT(RT_MAXG, true); else SPT_RT(RT_MAXG, false); }
+#undef SPT_RT
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }
@@ -529,6 +601,15 @@ extern "C" int spt_route_topk_logits(const float *logits, int ld, const float *b
     if (!prob || !token64 || !block64 || !coeff) return SPT_EINVAL;
     return route_topk_any(logits, token, block, offsets, pos, token64, block64, coeff, scale, n_tokens,
                           n_blocks, k, stream, ld, bias, prob);
+}
+
+extern "C" int spt_route_topk_counted(const float *logits, int ld, const float *bias, const int32_t *counts,
+                                      float *prob, int32_t *token, int32_t *block, int32_t *offsets,
+                                      int32_t *pos, long long *token64, long long *block64, float *coeff,
+                                      float scale, int n_tokens, int n_blocks, int k, void *stream) {
+    if (!counts || !prob || !token64 || !block64 || !coeff) return SPT_EINVAL;
+    return route_topk_any(logits, token, block, offsets, pos, token64, block64, coeff, scale, n_tokens,
+                          n_blocks, k, stream, ld, bias, prob, counts);
 }
 
 extern "C" int spt_route_coeff_backward(const float *dcoeff, const int32_t *pos, const int32_t *block,
@@ -565,6 +646,29 @@ extern "C" int spt_ffn_coeff_grad(const float *dot_main, const float *dot_act, i
     hipLaunchKernelGGL(ffn_coeff_grad_kernel, dim3((n_rows + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, dot_main, dot_act, width, du, u, dzt, z, token, coeff,
                        floor_value, out, n_rows, rank);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_ffn_router_backward(const float *dot_main, const float *dot_act, int width,
+                                       const float *du, const float *u, const float *dzt, const float *z,
+                                       const int32_t *pos, const int32_t *block, const float *coeff,
+                                       float floor_value, float scale, const float *prob, float *dlogit,
+                                       float *du_tok, float *z_tok, float *dcoeff, int n_tokens,
+                                       int n_blocks, int k, int rank, void *stream) {
+    if (!dot_main || !dot_act || !du || !u || !dzt || !z || !pos || !block || !coeff || !prob || !dlogit ||
+        !du_tok || !z_tok)
+        return SPT_EINVAL;
+    if (n_tokens <= 0 || width <= 0 || n_blocks <= 0 || k <= 0 || k > n_blocks) return SPT_EINVAL;
+    if (rank != 16 || n_blocks > RT_MAXG) return SPT_EUNSUP;
+    if (((reinterpret_cast<uintptr_t>(du) | reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(dzt) |
+          reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(du_tok) |
+          reinterpret_cast<uintptr_t>(z_tok)) & 15) != 0)
+        return SPT_ESHAPE;
+    const int per = RB_THREADS / 4;
+    hipLaunchKernelGGL(ffn_router_backward_kernel, dim3((n_tokens + per - 1) / per), dim3(RB_THREADS), 0,
+                       (hipStream_t)stream, dot_main, dot_act, width, du, u, dzt, z, pos, block, coeff,
+                       floor_value, scale, prob, dlogit, du_tok, z_tok, dcoeff, n_tokens, n_blocks, k);
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }

@@ -109,6 +109,8 @@ _PROTOTYPES = {
     'spt_rows_combine_bf16': ([_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_ffn_coeff_grad': ([_c_ptr, _c_ptr, _c_int] + [_c_ptr] * 6 + [_c_f32, _c_ptr, _c_int, _c_int, _c_ptr],
                            _c_int),
+    'spt_ffn_router_backward': ([_c_ptr, _c_ptr, _c_int] + [_c_ptr] * 7 + [_c_f32, _c_f32] + [_c_ptr] * 5
+                                + [_c_int] * 4 + [_c_ptr], _c_int),
     'spt_layernorm_form': ([_c_int] * 2, _c_int),
     'spt_layernorm_partial_rows': ([ctypes.c_longlong], _c_int),
     'spt_add_layernorm_forward': ([_c_ptr] * 8 + [ctypes.c_longlong, _c_int, _c_f32, _c_int, _c_ptr], _c_int),
@@ -119,6 +121,9 @@ _PROTOTYPES = {
                        _c_ptr, ctypes.c_longlong, _c_int] + [_c_ptr] * 2 + [_c_int, _c_ptr], _c_int),
     'spt_lora_down2': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int, _c_ptr, _c_int,
                         _c_ptr, ctypes.c_longlong, _c_int] + [_c_ptr] * 2 + [_c_int, _c_ptr], _c_int),
+    'spt_lora_down2_route': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int, _c_ptr, _c_int,
+                              _c_ptr, _c_int, _c_ptr, _c_ptr, ctypes.c_longlong, _c_int] + [_c_ptr] * 2
+                             + [_c_int, _c_ptr], _c_int),
     'spt_lora_down_grouped_cols': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, ctypes.c_longlong,
                                     _c_int, _c_ptr, _c_int, _c_ptr, ctypes.c_longlong, _c_ptr], _c_int),
     'spt_lora_down_tables': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int,
@@ -136,6 +141,7 @@ _PROTOTYPES = {
     'spt_route_topk': ([_c_ptr] * 5 + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_route_topk_coeff': ([_c_ptr] * 8 + [_c_f32] + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_route_topk_logits': ([_c_ptr, _c_int] + [_c_ptr] * 9 + [_c_f32] + [_c_int] * 3 + [_c_ptr], _c_int),
+    'spt_route_topk_counted': ([_c_ptr, _c_int] + [_c_ptr] * 10 + [_c_f32] + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_route_coeff_backward': ([_c_ptr] * 3 + [_c_f32, _c_ptr] + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_route_logit_backward': ([_c_ptr] * 3 + [_c_f32, _c_ptr, _c_ptr] + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_softmax_forward': ([_c_ptr] * 4 + [_c_int] * 3 + [_c_ptr], _c_int),
@@ -1685,12 +1691,21 @@ def route_topk_coeff(prob: torch.Tensor, k: int, scale: float):
 
 
 
-def route_topk_logits(logits: torch.Tensor, bias: torch.Tensor, n_blocks: int, k: int, scale: float):
+def route_counts_width(n_blocks: int) -> int:
+    """Block slots per row of the selection counts (``lora_down(route=...)``, ``route_topk_logits(counts=...)``)."""
+    return 4 if n_blocks <= 4 else 8
+
+
+def route_topk_logits(logits: torch.Tensor, bias: torch.Tensor, n_blocks: int, k: int, scale: float,
+                      counts: torch.Tensor = None):
     """``spt_route_topk_logits``: `route_topk_coeff` from the router's LOGITS (x @ W^T without
     bias: [T, >= n_blocks], unit inner stride, 16-byte aligned rows -- a view of a wider matrix);
     the probabilities sigmoid(logits + bias) are formed in the same launch (the top-k ranks logits + bias:
     the ranking of the probabilities wherever two differ; equal probabilities of distinct logits go to
     the larger logit).
+    ``counts`` (``spt_route_topk_counted``): the per-group selection counts int32 [ceil(T / 16), 4 | 8] that
+    ``lora_down(..., route=(bias, k))`` left beside these logits -- the same outputs, without every
+    workgroup ranking every token.
     -> (prob [T, n_blocks], token, block, offsets, pos, token64, block64, coeff)."""
     _check_type(logits, torch.float32, 'logits')
     _require(logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1 and logits.size(1) >= n_blocks
@@ -1713,10 +1728,21 @@ def route_topk_logits(logits: torch.Tensor, bias: torch.Tensor, n_blocks: int, k
         token64 = torch.empty([T * k], dtype=torch.int64, device=dev)
         block64 = torch.empty([T * k], dtype=torch.int64, device=dev)
         coeff = torch.empty([T * k], dtype=torch.float32, device=dev)
-        rc = lib.spt_route_topk_logits(logits.data_ptr(), logits.stride(0), _ptr(bias), prob.data_ptr(),
-                                       token.data_ptr(), block.data_ptr(), offsets.data_ptr(), pos.data_ptr(),
-                                       token64.data_ptr(), block64.data_ptr(), coeff.data_ptr(), float(scale),
-                                       T, G, k, _stream(dev))
+        if counts is not None:
+            _check_type(counts, torch.int32, 'counts')
+            _require(counts.is_contiguous() and counts.device == dev
+                     and counts.shape == ((T + 15) // 16, route_counts_width(G)),
+                     'route_topk_logits: counts int32 [ceil(T / 16), 4 | 8] of these logits')
+            rc = lib.spt_route_topk_counted(logits.data_ptr(), logits.stride(0), _ptr(bias), counts.data_ptr(),
+                                            prob.data_ptr(), token.data_ptr(), block.data_ptr(),
+                                            offsets.data_ptr(), pos.data_ptr(), token64.data_ptr(),
+                                            block64.data_ptr(), coeff.data_ptr(), float(scale), T, G, k,
+                                            _stream(dev))
+        else:
+            rc = lib.spt_route_topk_logits(logits.data_ptr(), logits.stride(0), _ptr(bias), prob.data_ptr(),
+                                           token.data_ptr(), block.data_ptr(), offsets.data_ptr(), pos.data_ptr(),
+                                           token64.data_ptr(), block64.data_ptr(), coeff.data_ptr(), float(scale),
+                                           T, G, k, _stream(dev))
     if rc != 0:
         _raise(lib, rc, 'route_topk_logits')
     return prob, token, block, offsets, pos, token64, block64, coeff
@@ -1925,7 +1951,7 @@ def lora_down_supported(x: torch.Tensor, table: torch.Tensor) -> bool:
 
 def lora_down(x: torch.Tensor, table: torch.Tensor, want_image: bool = False,
               want_norms: bool = False, block_major: bool = False, out: torch.Tensor = None,
-              exact: bool = False, table2: torch.Tensor = None):
+              exact: bool = False, table2: torch.Tensor = None, route=None):
     """u = x @ table for a tall x [rows, K] and a table [K, n] of a few columns, as ONE pass over x
     (``spt_lora_down``); the same pass can also leave x's split image (:class:`SplitImage`) and its
     row 2-norms.  Returns u, or (u, image | None, norms | None) when a by-product is asked for.
@@ -1934,13 +1960,18 @@ def lora_down(x: torch.Tensor, table: torch.Tensor, want_image: bool = False,
     stride, any row stride: a column slice of a wider matrix).  ``exact``: u in exact fp32 instead of
     split-bf16 products (for the u in front of a ReLU GEMM: include/spt_hip.h).  ``table2``
     (``spt_lora_down2``; needs ``block_major`` and ``exact``): a row-major [n2 <= 16, K] matrix (an nn.Linear
-    weight) whose product x @ table2.T fills one more block: u[-1][:, :n2]."""
+    weight) whose product x @ table2.T fills one more block: u[-1][:, :n2].  ``route`` = (bias | None, k)
+    (``spt_lora_down2_route``; ``table2`` the routed FFN's router [n_blocks <= 8, K], one rank-16 table): the
+    launch also leaves the per-group selection counts of its logits + bias, int32
+    [ceil(rows / 16), 4 | 8], for ``route_topk_logits(counts=...)``; returns (u, image | None, norms | None,
+    counts)."""
     _require(lora_down_supported(x, table), 'lora_down: see lora_down_supported')
     table = table.contiguous()
     rows, k = x.shape
     n = table.size(1)
     dev = _same_device(x, table)
     lib = load_library()
+    _require(route is None or table2 is not None, 'lora_down: route needs table2 (the router)')
     if table2 is not None:
         _check_type(table2, torch.float32, 'table2')
         _require(block_major and out is None and table2.dim() == 2 and table2.is_contiguous()
@@ -1955,12 +1986,29 @@ def lora_down(x: torch.Tensor, table: torch.Tensor, want_image: bool = False,
                                                device=dev), rows, k)
             if want_norms:
                 norms = torch.empty([rows], dtype=torch.float32, device=dev)
-            rc = lib.spt_lora_down2(x.data_ptr(), x.stride(0), rows, k, table.data_ptr(), n,
-                                    table2.data_ptr(), table2.size(0), u.data_ptr(), 0, 1,
-                                    image.buffer.data_ptr() if want_image else None, _ptr(norms),
-                                    int(bool(exact)), _stream(dev))
+            if route is not None:
+                r_bias, r_k = route
+                G = table2.size(0)
+                _require(n == 16 and G <= 8 and 0 < r_k <= G, 'lora_down: route with one rank-16 table, <= 8 blocks')
+                if r_bias is not None:
+                    _check_type(r_bias, torch.float32, 'route bias')
+                    _require(r_bias.is_contiguous() and r_bias.numel() == G and r_bias.device == dev,
+                             'route bias: [n_blocks]')
+                counts = torch.empty([(rows + 15) // 16, route_counts_width(G)], dtype=torch.int32, device=dev)
+                rc = lib.spt_lora_down2_route(x.data_ptr(), x.stride(0), rows, k, table.data_ptr(), n,
+                                              table2.data_ptr(), G, _ptr(r_bias), int(r_k), counts.data_ptr(),
+                                              u.data_ptr(), 0, 1,
+                                              image.buffer.data_ptr() if want_image else None, _ptr(norms),
+                                              int(bool(exact)), _stream(dev))
+            else:
+                rc = lib.spt_lora_down2(x.data_ptr(), x.stride(0), rows, k, table.data_ptr(), n,
+                                        table2.data_ptr(), table2.size(0), u.data_ptr(), 0, 1,
+                                        image.buffer.data_ptr() if want_image else None, _ptr(norms),
+                                        int(bool(exact)), _stream(dev))
         if rc != 0:
             _raise(lib, rc, 'lora_down2')
+        if route is not None:
+            return u, image, norms, counts
         return (u, image, norms) if (want_image or want_norms) else u
     with _on(dev):
         if out is not None:
@@ -2194,9 +2242,15 @@ def layernorm_backward(s: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, m
 
 def ffn_coeff_grad(dot_main: torch.Tensor, dot_act: torch.Tensor, du: torch.Tensor, u: torch.Tensor,
                    dzt: torch.Tensor, z: torch.Tensor, token: torch.Tensor, coeff: torch.Tensor,
-                   floor_value: float) -> torch.Tensor:
+                   floor_value: float, router=None, want_rows: bool = False):
     """``spt_ffn_coeff_grad``: (sum dot_main + sum dot_act - <du, u[token]> - <dzt[token], z>) /
-    max(coeff, floor) per row, one launch (the routed FFN's router-coefficient gradient)."""
+    max(coeff, floor) per row, one launch (the routed FFN's router-coefficient gradient).
+    ``router`` = (pos [T, k], block [T * k], prob [T, n_blocks], scale) (``spt_ffn_router_backward``; rank 16,
+    <= 8 blocks; `token` is implied by `pos` and not read): the same launch carries the gradient on through
+    the bucketing and the sigmoid and sums du and z per token
+    -> (dlogit [T, n_blocks], du_tok [T, r], z_tok [T, r], per-row gradient [P] if ``want_rows`` else None),
+    each bit for bit what ffn_coeff_grad, rows_combine(du, pos), rows_combine(z, pos) and
+    route_coeff_backward(..., prob=prob) give."""
     for t in (dot_main, dot_act, du, u, dzt, z, coeff):
         _check_type(t, torch.float32, 'ffn_coeff_grad operand')
         _require(t.is_cuda and t.is_contiguous(), 'ffn_coeff_grad: contiguous CUDA operands')
@@ -2207,6 +2261,31 @@ def ffn_coeff_grad(dot_main: torch.Tensor, dot_act: torch.Tensor, du: torch.Tens
              and r % 4 == 0, 'ffn_coeff_grad: shapes')
     dev = _same_device(dot_main, du, u, token, coeff)
     lib = load_library()
+    if router is not None:
+        pos, block, prob, scale = router
+        _check_type(pos, torch.int32, 'pos')
+        _check_type(block, torch.int32, 'block')
+        _check_type(prob, torch.float32, 'prob')
+        _require(pos.dim() == 2 and pos.is_contiguous() and block.is_contiguous() and prob.is_contiguous()
+                 and prob.dim() == 2 and pos.numel() == block.numel() == P and pos.size(0) == prob.size(0) == u.size(0)
+                 and r == 16 and prob.size(1) <= 8 and 0 < pos.size(1) <= prob.size(1),
+                 'ffn_coeff_grad: router = (pos [T, k], block [T * k], prob [T, <= 8], scale), rank 16')
+        T, k = pos.shape
+        _same_device(dot_main, pos, block, prob)
+        with _on(dev):
+            dlogit = torch.empty([T, prob.size(1)], dtype=torch.float32, device=dev)
+            du_tok = torch.empty([T, r], dtype=torch.float32, device=dev)
+            z_tok = torch.empty([T, r], dtype=torch.float32, device=dev)
+            out = torch.empty([P], dtype=torch.float32, device=dev) if want_rows else None
+            rc = lib.spt_ffn_router_backward(dot_main.data_ptr(), dot_act.data_ptr(), dot_main.size(1),
+                                             du.data_ptr(), u.data_ptr(), dzt.data_ptr(), z.data_ptr(),
+                                             pos.data_ptr(), block.data_ptr(), coeff.data_ptr(),
+                                             float(floor_value), float(scale), prob.data_ptr(),
+                                             dlogit.data_ptr(), du_tok.data_ptr(), z_tok.data_ptr(), _ptr(out),
+                                             T, prob.size(1), k, r, _stream(dev))
+        if rc != 0:
+            _raise(lib, rc, 'ffn_router_backward')
+        return dlogit, du_tok, z_tok, out
     with _on(dev):
         out = torch.empty([P], dtype=torch.float32, device=dev)
         rc = lib.spt_ffn_coeff_grad(dot_main.data_ptr(), dot_act.data_ptr(), dot_main.size(1),

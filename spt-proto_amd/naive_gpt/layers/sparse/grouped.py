@@ -110,6 +110,10 @@ COEFF_FLOOR = 1e-12
 # box (the same for x: +0.26 ms, for dy: +-0: both keep their images)
 H_A32 = os.environ.get('SPT_H_A32', '1') != '0'
 ROUTER_RIDES = os.environ.get('SPT_ROUTER_RIDES', '1') != '0'
+# the router's small launches: the selection counts ride the logits' launch (forward), and
+# coefficient gradient + the two [T, r] combines + d logit are one launch (backward).  '0': the separate calls.
+ROUTER_COUNTS = os.environ.get('SPT_ROUTER_COUNTS', '1') != '0'
+ROUTER_BACKWARD_FUSED = os.environ.get('SPT_ROUTER_BACKWARD_FUSED', '1') != '0'
 
 
 def _floor(coeff: torch.Tensor) -> torch.Tensor:
@@ -689,13 +693,23 @@ class RoutedLoRAFFN(torch.autograd.Function):
             # launch, exact fp32: the top-k must not depend on a split's 2^-16), x's image and row
             # norms; the sigmoid is formed inside the routing launch.  (As torch operators: a library
             # GEMM with 4 output columns and a sigmoid pass, ~20 us per layer.)
+            # The same launch ranks its 16 rows' logits + bias and leaves the per-group selection counts:
+            # the routing launch sums those instead of ranking every token in every workgroup.
             ext.note_path('router', 'rides_lora_down')
-            pack = ext.lora_down(x, l1, want_image=imgs, want_norms=relu, block_major=True, exact=True,
-                                 table2=rw)
-            pack, x_img, x_norm = pack if isinstance(pack, tuple) else (pack, None, None)
+            counts = None
+            if ROUTER_COUNTS:
+                ext.note_path('router_counts', 'ride_lora_down')
+                pack, x_img, x_norm, counts = ext.lora_down(
+                    x, l1, want_image=imgs, want_norms=relu, block_major=True, exact=True, table2=rw,
+                    route=(rb, top_k))
+            else:
+                ext.note_path('router_counts', 'recounted')
+                pack = ext.lora_down(x, l1, want_image=imgs, want_norms=relu, block_major=True, exact=True,
+                                     table2=rw)
+                pack, x_img, x_norm = pack if isinstance(pack, tuple) else (pack, None, None)
             u = pack[0]
             prob, token, block, offsets, pos, token_long, block_long, coeff = \
-                ext.route_topk_logits(pack[1], rb, nb, top_k, 2.0)
+                ext.route_topk_logits(pack[1], rb, nb, top_k, 2.0, counts=counts)
             ext.note_path('route_topk', 'kernel')
             bk = Buckets(token=token, token_long=token_long, block=block_long, offsets=offsets,
                          coeff=coeff, n_blocks=nb, pos=pos)
@@ -761,17 +775,25 @@ class RoutedLoRAFFN(torch.autograd.Function):
         # s = c (x W1^T + b1) + u R1^T; the LoRA parts of both are [*, r] dots:
         # <dzt L2_g^T, h> = <dzt, z> and <ds, u R1_g^T> = <du, u>
         # (dot_main + dot_act - <du, u[token]> - <dzt[token], z>) / _floor(coeff), one launch
-        grad_coeff = ext.ffn_coeff_grad(dot_main, dot_act, du, u, dzt, z, bk.token, coeff, COEFF_FLOOR)
         # LoRA tables (before the last GEMM: ds [P, bs] is released as soon as that has read it --
         # the step's peak memory is here, with h, ds, dxs and grad_x alive)
-        du_tok = ext.rows_combine(du, bk.pos)                                # [T, r]: du[pos].sum(1)
         # (two pairs of equal shape: one pair of launches each)
         from naive_gpt.layers.tuning.lora import tall_tn_many
-        z_tok = ext.rows_combine(z, bk.pos)
-        router_rides = grad_coeff.is_cuda and nb <= 8 and d % 4 == 0
+        router_rides = du.is_cuda and nb <= 8 and d % 4 == 0
         dlogit = grad_rw = None
-        if router_rides:
-            dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
+        if router_rides and ROUTER_BACKWARD_FUSED and rank == 16:
+            # one launch: the coefficient gradient stays in registers on its way to d logit, and the
+            # rows it reads of du and z are the ones the two [T, r] sums need
+            ext.note_path('router_backward', 'one_launch')
+            dlogit, du_tok, z_tok, _ = ext.ffn_coeff_grad(dot_main, dot_act, du, u, dzt, z, bk.token, coeff,
+                                                          COEFF_FLOOR, router=(bk.pos, block, prob, 2.0))
+        else:
+            ext.note_path('router_backward', 'separate')
+            grad_coeff = ext.ffn_coeff_grad(dot_main, dot_act, du, u, dzt, z, bk.token, coeff, COEFF_FLOOR)
+            du_tok = ext.rows_combine(du, bk.pos)                            # [T, r]: du[pos].sum(1)
+            z_tok = ext.rows_combine(z, bk.pos)
+            if router_rides:
+                dlogit = ext.route_coeff_backward(grad_coeff.contiguous(), bk.pos, block, 2.0, nb, prob=prob)
         if ctx.origin_module is not None:
             # The two readers of x are the gradients of L1 (x^T du) and of the router's weight (dlogit^T x).
             # From the norm's input, statistics and parameters one pass forms x on load and feeds both

@@ -264,6 +264,39 @@ def _stream(dev) -> int:
     return torch._C._cuda_getCurrentRawStream(idx if idx is not None else torch._C._cuda_getDevice())
 
 
+_CAPTURE_INFO = None
+
+
+def capture_tag(dev=None) -> int:
+    """0 when torch's current stream on `dev` (a torch.device; default: the current device) is not
+    being captured into a HIP graph, else a number that names THAT capture
+    (hipStreamGetCaptureInfo's id + 1, asked of the HIP runtime this library links).  It is the
+    stream `_stream(dev)` hands the kernels.  Every host-side memo below tags its entries with it
+    and serves an entry only under the tag it was made with.  Outside -> inside: a hit would leave
+    the launch that made the by-product out of the graph, and a replay on new contents of the same
+    buffers would read the old by-product at its old address (the version counter moves, but
+    nothing in a graph looks at it).  Inside -> outside, or into another capture: the entry's
+    memory belongs to that graph's pool and is rewritten by every replay.  Eager callers on the
+    current device pay one C call of torch's, and the memos ask only where everything else about
+    an entry already matches, or when they make one."""
+    global _CAPTURE_INFO
+    idx = None if dev is None else dev.index
+    if idx is None or idx == torch._C._cuda_getDevice():
+        if not torch._C._cuda_isCurrentStreamCapturing():
+            return 0
+        idx = torch._C._cuda_getDevice()
+    if _CAPTURE_INFO is None:
+        fn = load_library().hipStreamGetCaptureInfo
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_ulonglong)]
+        fn.restype = ctypes.c_int
+        _CAPTURE_INFO = fn
+    status, ident = ctypes.c_int(0), ctypes.c_ulonglong(0)
+    rc = _CAPTURE_INFO(torch._C._cuda_getCurrentRawStream(idx), ctypes.byref(status), ctypes.byref(ident))
+    if rc != 0:
+        raise RuntimeError('naive_gpt.ext: hipStreamGetCaptureInfo -> {}'.format(rc))
+    return ident.value + 1 if status.value != 0 else 0
+
+
 def held_by_caches() -> list:
     """Every device tensor the module-level caches of this package hold for later calls: frozen
     weights' row norms and (SPT_WEIGHT_IMAGES=keep) images.  A captured HIP graph that read one of
@@ -869,13 +902,17 @@ def transposed_for(indptr: torch.Tensor, indices: torch.Tensor, d_head: int = 64
     """``csr_transpose`` memoised on the ``indices`` tensor object itself (keyed by the
     tensors' in-place version counters and the head size), so the A^T products of one
     backward pass -- grad_K in sddmm's backward, grad_V in spmm's -- share one build.  The
-    cache dies with the tensor."""
+    cache dies with the tensor.  A build made outside a graph capture is not served inside one,
+    nor the other way round (`capture_tag`)."""
     key = (indices._version, indptr.data_ptr(), indptr._version, int(d_head))
     cached = getattr(indices, '_spt_transposed', None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
+    tag = None
+    if cached is not None and cached[0] == key:         # (the tag is asked only where all else matches)
+        tag = capture_tag(indices.device)
+        if cached[2] == tag:
+            return cached[1]
     buf = csr_transpose(indptr, indices, d_head)
-    indices._spt_transposed = (key, buf)
+    indices._spt_transposed = (key, buf, capture_tag(indices.device) if tag is None else tag)
     return buf
 
 
@@ -1237,7 +1274,10 @@ def split_bf16(x: torch.Tensor) -> SplitImage:
 # tensor: the first splits it, the other two find the image here.  An entry is identified by
 # the OWNER object (the tensor the layer was called with, held through a weak reference -- no
 # lifetime is extended, and an address handed to another tensor cannot alias) and its
-# `_version` (every in-place write moves it).  Two entries: they are as large as activations.
+# `_version` (every in-place write moves it), its shape and the capture it was made in
+# (`capture_tag`: q / k / v share one image inside a capture too, but a capture never reads an
+# image that eager code made, nor eager code one of a graph's).  Two entries: they are as large as
+# activations.
 _IMAGE_CACHE = collections.OrderedDict()
 IMAGE_CACHE_ENTRIES = 2
 
@@ -1250,12 +1290,15 @@ def image_of(x: torch.Tensor, owner: torch.Tensor = None) -> SplitImage:
         return split_bf16(x)
     key = id(owner)
     hit = _IMAGE_CACHE.get(key)
-    if hit is not None and hit[0]() is owner and hit[1] == (owner._version, tuple(x.shape)):
-        _IMAGE_CACHE.move_to_end(key)
-        return hit[2]
+    stamp, tag = (owner._version, tuple(x.shape)), None
+    if hit is not None and hit[0]() is owner and hit[1][:2] == stamp:    # (the tag: only where all else matches)
+        tag = capture_tag(x.device)
+        if hit[1][2] == tag:
+            _IMAGE_CACHE.move_to_end(key)
+            return hit[2]
     img = split_bf16(x)
     _IMAGE_CACHE[key] = (weakref.ref(owner, lambda _, k=key: _IMAGE_CACHE.pop(k, None)),
-                         (owner._version, tuple(x.shape)), img)
+                         stamp + (capture_tag(x.device) if tag is None else tag,), img)
     _IMAGE_CACHE.move_to_end(key)
     while len(_IMAGE_CACHE) > IMAGE_CACHE_ENTRIES:
         _IMAGE_CACHE.popitem(last=False)
@@ -1268,7 +1311,8 @@ def cached_image(x: torch.Tensor, owner: torch.Tensor = None):
     if owner.is_inference():
         return None
     hit = _IMAGE_CACHE.get(id(owner))
-    if hit is not None and hit[0]() is owner and hit[1] == (owner._version, tuple(x.shape)):
+    if hit is not None and hit[0]() is owner and hit[1][:2] == (owner._version, tuple(x.shape)) \
+            and hit[1][2] == capture_tag(x.device):
         return hit[2]
     return None
 
@@ -1280,7 +1324,7 @@ def put_image(x: torch.Tensor, owner: torch.Tensor, img: SplitImage) -> None:
         return
     key = id(owner)
     _IMAGE_CACHE[key] = (weakref.ref(owner, lambda _, k=key: _IMAGE_CACHE.pop(k, None)),
-                         (owner._version, tuple(x.shape)), img)
+                         (owner._version, tuple(x.shape), capture_tag(x.device)), img)
     _IMAGE_CACHE.move_to_end(key)
     while len(_IMAGE_CACHE) > IMAGE_CACHE_ENTRIES:
         _IMAGE_CACHE.popitem(last=False)
@@ -1299,7 +1343,14 @@ def drop_images():
 # life of the parameter (dropped when `_version` moves).
 class _PerParameter:
     """{parameter -> value} keyed by identity (a tensor's `==` is elementwise, which rules out
-    weakref.WeakKeyDictionary); an entry dies with its parameter or when `_version` moves."""
+    weakref.WeakKeyDictionary); an entry dies with its parameter or when `_version` moves.
+
+    Entries carry the `capture_tag` they were made under.  Eager code is served eager entries only.
+    A graph capture is served its own entries and, for a parameter that does not require a
+    gradient, eager ones: nothing in a captured step writes a frozen weight, and what the warm-up
+    computed need not be computed again by every replay (`held_by_caches` keeps it alive for the
+    graph).  A TRAINED weight's eager entry is not served to a capture: the in-graph optimiser
+    moves the weight between two replays, and the by-product has to be made inside the graph."""
 
     def __init__(self):
         self.data = {}
@@ -1307,13 +1358,15 @@ class _PerParameter:
     def get(self, w):
         hit = self.data.get(id(w))
         if hit is not None and hit[0]() is w and hit[1] == (w.data_ptr(), w._version):
-            return hit[2]
+            tag = capture_tag(w.device)
+            if hit[3] == tag or (hit[3] == 0 and not w.requires_grad):
+                return hit[2]
         return None
 
     def put(self, w, value):
         key = id(w)
         self.data[key] = (weakref.ref(w, lambda _, k=key: self.data.pop(k, None)),
-                          (w.data_ptr(), w._version), value)
+                          (w.data_ptr(), w._version), value, capture_tag(w.device))
 
     def clear(self):
         self.data.clear()

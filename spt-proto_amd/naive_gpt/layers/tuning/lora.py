@@ -165,13 +165,17 @@ def prepare_shared(x: torch.Tensor, linears) -> None:
             return
         u, image, _ = ext.lora_down(x2, table, want_image=True, block_major=True)
     ext.put_image(x2, x, image)
-    _SHARED[id(x)] = (weakref.ref(x, lambda _, k=id(x): _SHARED.pop(k, None)), x._version,
-                      {id(l): u[i] for i, l in enumerate(lefts)})
+    _SHARED[id(x)] = (weakref.ref(x, lambda _, k=id(x): _SHARED.pop(k, None)), (x._version, ext.capture_tag(x.device)),
+                      {id(l): u[i] for i, l in enumerate(lefts)}, ext.capture_tag)
 
 
 def _shared_u(x: torch.Tensor, left: torch.Tensor):
     hit = _SHARED.get(id(x))
-    if hit is None or hit[0]() is not x or hit[1] != x._version:
+    if hit is None or hit[0]() is not x or hit[1][0] != x._version:
+        return None
+    # (products made outside a graph capture are not served inside one, nor the other way round:
+    # ext.capture_tag, which the entry carries -- no import on this path)
+    if hit[1][1] != hit[3](x.device):
         return None
     return hit[2].get(id(left))
 

@@ -122,10 +122,12 @@ def same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
 def fresh_caches(*indices):
     """Empty every cache that could carry a result from one run into the next: the split images,
     weight images and weight norms of ext, the csr_transpose memo on each given `indices` tensor,
-    and the attention layers' indptr cache."""
+    the adapters' shared down products, and the attention layers' indptr cache."""
     from naive_gpt import ext
     from naive_gpt.layers.sparse.attention import _SparseCore
+    from naive_gpt.layers.tuning import lora
     ext.drop_images()
+    lora._SHARED.clear()
     for t in indices:
         if hasattr(t, '_spt_transposed'):
             del t._spt_transposed

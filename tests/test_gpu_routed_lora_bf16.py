@@ -506,6 +506,25 @@ def test_graph_capture_replays_bitwise(kind, monkeypatch):
     assert torch.equal(y_static, y_eager)
     for g, ge in zip([x.grad] + [p.grad for p in params], grads_eager):
         assert torch.equal(g, ge)
+    # The same graph on new contents of its buffers: new tokens, a new upstream gradient, and every
+    # trained parameter nudged in place, as the in-graph optimiser moves it between two replays.
+    with torch.no_grad():
+        x.copy_(torch.randn([T, d], device='cuda').to(BF))
+        w.copy_(torch.randn([T, d], device='cuda').to(BF))
+        for p in params:
+            if p.requires_grad:
+                p.add_((0.01 * torch.randn(p.shape, device='cuda')).to(p.dtype))
+    graph.replay()
+    torch.cuda.synchronize()
+    y_replay = y_static.detach().clone()
+    grads_replay = [None if g is None else g.clone() for g in [x.grad] + [p.grad for p in params]]
+    y_new = step().detach().clone()
+    assert not torch.equal(y_new, y_eager), 'the new contents changed nothing'
+    assert torch.equal(y_replay, y_new)
+    for i, (g, ge) in enumerate(zip(grads_replay, [x.grad] + [p.grad for p in params])):
+        assert (g is None) == (ge is None)
+        if g is not None:
+            assert torch.equal(g, ge), 'gradient %d' % i
 
 
 @pytest.mark.parametrize('kind', ['opt', 'llama'])

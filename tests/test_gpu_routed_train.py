@@ -269,8 +269,7 @@ def test_two_adamw_steps_equal_the_loop(kind, trainable, monkeypatch):
             assert _scaled_close(g, g0), name
 
 
-@pytest.mark.parametrize('kind', ['opt', 'llama'])
-def test_graph_capture_of_forward_and_backward(kind, trainable):
+def _graph_capture_of_forward_and_backward(kind):
     from naive_gpt import layers
     torch.manual_seed(13)
     d, dff, bs, T = 256, 1024, 128, 512
@@ -314,3 +313,45 @@ def test_graph_capture_of_forward_and_backward(kind, trainable):
         assert (g is None) == (ge is None)
         if g is not None:
             assert torch.allclose(g, ge, rtol=1e-6, atol=1e-7 * ge.abs().max().item())
+    # The same graph on new contents of its buffers: new tokens, a new upstream gradient, and every
+    # trained parameter nudged in place, as the in-graph optimiser moves it between two replays.
+    # Whatever the capture took from a cache that the warm-up filled (row norms, kept images of the
+    # weights) must follow: the replay equals an eager step on the new contents.
+    with torch.no_grad():
+        x.copy_(torch.randn_like(x))
+        w.copy_(torch.randn_like(w))
+        for p in params:
+            if p.requires_grad:
+                p.add_(0.01 * torch.randn_like(p))
+    graph.replay()
+    torch.cuda.synchronize()
+    y_replay = y_static.detach().clone()
+    grads_replay = [None if g is None else g.clone() for g in [x.grad] + [p.grad for p in params]]
+    y_new = step().detach().clone()
+    grads_new = [x.grad] + [p.grad for p in params]
+    assert not torch.equal(y_new, y_eager), 'the new contents changed nothing'
+    assert torch.allclose(y_replay, y_new, rtol=1e-6, atol=1e-7 * y_new.abs().max().item())
+    for i, (g, ge) in enumerate(zip(grads_replay, grads_new)):
+        assert (g is None) == (ge is None)
+        if g is not None:
+            assert torch.allclose(g, ge, rtol=1e-6, atol=1e-7 * ge.abs().max().item()), 'gradient %d' % i
+
+
+@pytest.mark.parametrize('kind', ['opt', 'llama'])
+def test_graph_capture_of_forward_and_backward(kind, trainable):
+    _graph_capture_of_forward_and_backward(kind)
+
+
+@pytest.mark.parametrize('kind', ['opt', 'llama'])
+def test_graph_capture_with_kept_weight_images(kind, trainable, monkeypatch):
+    """SPT_WEIGHT_IMAGES=keep: images and row norms of weights are kept with the parameter.  The
+    trained weights' must follow the nudged weights all the same: the trainable path forms them
+    from the weights' values at the call, and a capture is never served what eager code kept for a
+    weight that requires a gradient (ext._PerParameter)."""
+    from naive_gpt import ext
+    monkeypatch.setattr(ext, 'KEEP_WEIGHT_IMAGES', True)
+    ext.drop_images()
+    try:
+        _graph_capture_of_forward_and_backward(kind)
+    finally:
+        ext.drop_images()

@@ -522,6 +522,25 @@ int spt_grouped_gemm_pdot_width(int n);
  * into its bf16 parts inside the kernel -- no image of the activation is needed at all;
  * 0 = from the fp32 operands through registers (k % 32 != 0, or no w_image). */
 int spt_grouped_gemm_image_path(const SptGroupedGemm *desc);
+/* spt_grouped_gemm_fused on a weight stored as IEEE halves (additive under ABI 40): the same
+ * descriptor with the same layout, `w` pointing at fp16 elements (8-byte aligned) with the same
+ * ELEMENT strides w_group_stride / w_ldn / w_ldk.  The matrix cores never multiply the weight's
+ * value but its split image, and for a half x the split is exact (11 significant bits: hi takes
+ * 8, lo the other 3), so `w_image` made by spt_split_f16 is byte for byte the image of the fp32
+ * upcast and every output bit is that of spt_grouped_gemm_fused on the upcast weight.  The k-loops
+ * read w_image alone; `w` itself is read only by the ReLU epilogue's near-the-kink recomputation,
+ * which widens the halves it loads and adds in the same order.  Requires w_image and a usable image
+ * path (spt_grouped_gemm_image_path_w16(desc) != 0; SPT_EUNSUP otherwise: halves have no
+ * register-operand form).  One form more than spt_grouped_gemm_image_path covers: the segmented contraction
+ * (a_seg_k > 0, r <= 64, b2_seg_stride; SPT_EPI_PLAIN, a_image NULL), which a fp32 weight runs
+ * through registers, runs here from w_image and the fp32 rows of `a` (16-byte aligned, lda % 4 == 0)
+ * -- the same k-steps in the same order, the same bits.  Always the default kernels (SPT_GEMM_RING is
+ * not consulted). */
+int spt_grouped_gemm_fused_w16(const SptGroupedGemm *desc, void *stream);
+/* spt_grouped_gemm_image_path for spt_grouped_gemm_fused_w16: 0 = the entry refuses `desc`
+ * (SPT_EUNSUP), 1 / 2 as above -- 2 also for the segmented contraction, which halves alone run from
+ * the image. */
+int spt_grouped_gemm_image_path_w16(const SptGroupedGemm *desc);
 
 /*
  * The weight gradient of a grouped linear (ABI 40): a grouped product whose contraction runs over
@@ -637,6 +656,11 @@ int spt_grouped_gemm_wgrad_bf16(const void *g, long long ldg, const int32_t *gat
 size_t spt_split_bf16_bytes(long long rows, int cols);
 int spt_split_bf16(const float *src, void *image, long long rows, int cols, long long ld,
                    void *stream);
+/* The same image from a matrix of IEEE halves (additive under ABI 40; ld % 8 == 0, 16-byte aligned:
+ * eight halves per load): every half is widened to fp32 (exact) and split as above, so the image is
+ * byte for byte spt_split_bf16's of the fp32 upcast, made from half the bytes.  hi + lo == x exactly. */
+int spt_split_f16(const void *src_f16, void *image, long long rows, int cols, long long ld,
+                  void *stream);
 
 /*
  * The rank-r down product of the LoRA adapters (naive_gpt/layers/tuning/lora.py:70-80,

@@ -81,7 +81,18 @@ struct GroupedArgs {
     long long a_rowb, w_rowb;
     long long w_grow;       // image rows / 128-byte blocks from W_g(0, 0) to W_{g+1}(0, 0)
     int w_gblk;
+    // spt_grouped_gemm_fused_w16: `w` holds IEEE halves (same element strides).  The k-loops read the
+    // image alone; only gg_exact_preact reads `w` itself.  (In the struct's tail padding: the argument
+    // block of every kernel keeps its size and offsets.)
+    int w_f16;
 };
+
+// four IEEE halves (8-byte aligned) / one -> fp32: exact, every half is an fp32 value
+__device__ __forceinline__ float4 gg_h4(const _Float16 *p) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const h4 v = *reinterpret_cast<const h4 *>(p);
+    return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+}
 
 __device__ __forceinline__ float act_forward(int act, float s) {
     if (act == ACT_RELU) return fmaxf(s, 0.0f);
@@ -104,12 +115,18 @@ __device__ __forceinline__ float act_derivative(int act, float s) {
 // BATCHED: the k-contiguous weights' four passes of loads in flight together (relu_fix_kernel; the
 // epilogue's own rare fallback keeps the compact loop: inlined there the batched form cost the
 // activation GEMM registers)
-template <bool BATCHED = false>
+// w_f16 (wave-uniform): the weight's elements are halves, widened as they are loaded -- the same
+// values in the same order of additions, so the same bits as from the fp32 upcast of that weight.
+// (HALVES = false: a caller whose `w` is never halves -- the bf16-storage kernels -- keeps its code)
+template <bool BATCHED = false, bool HALVES = true>
 __device__ __forceinline__ float gg_exact_preact(const GroupedArgs &g, int bucket, int p, int n,
                                                  int lane) {
+    const bool w_f16 = HALVES && g.w_f16;
     const long long src = g.gather ? g.gather[p] : p;
     const float *ar = g.a + src * g.lda;
+    // (the same element strides at either width; of the two typed pointers only the weight's own is read)
     const float *wr = g.w + (size_t)bucket * g.gstride + (size_t)n * g.ldn;
+    const _Float16 *wh = reinterpret_cast<const _Float16 *>(g.w) + (size_t)bucket * g.gstride + (size_t)n * g.ldn;
     float part = 0.0f;
     if (BATCHED && g.ldk == 1) {
         // four passes' loads in flight together (clamped addresses, zeroed past K): as one load pair
@@ -121,7 +138,7 @@ __device__ __forceinline__ float gg_exact_preact(const GroupedArgs &g, int bucke
             for (int i = 0; i < 4; i++) {
                 const int k = min(k0 + 256 * i, g.K - 4);
                 x[i] = *reinterpret_cast<const float4 *>(ar + k);
-                y[i] = *reinterpret_cast<const float4 *>(wr + k);
+                y[i] = w_f16 ? gg_h4(wh + k) : *reinterpret_cast<const float4 *>(wr + k);
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
@@ -135,7 +152,14 @@ __device__ __forceinline__ float gg_exact_preact(const GroupedArgs &g, int bucke
         for (int k = 4 * lane; k < g.K; k += 256) {
             const float4 x = *reinterpret_cast<const float4 *>(ar + k);
             float4 y;
-            if (g.ldk == 1) {
+            if (w_f16) {
+                if (g.ldk == 1) {
+                    y = gg_h4(wh + k);
+                } else {
+                    y.x = (float)wh[(size_t)k * g.ldk]; y.y = (float)wh[(size_t)(k + 1) * g.ldk];
+                    y.z = (float)wh[(size_t)(k + 2) * g.ldk]; y.w = (float)wh[(size_t)(k + 3) * g.ldk];
+                }
+            } else if (g.ldk == 1) {
                 y = *reinterpret_cast<const float4 *>(wr + k);
             } else {            // n-contiguous weights: a strided column
                 y.x = wr[(size_t)k * g.ldk]; y.y = wr[(size_t)(k + 1) * g.ldk];
@@ -194,8 +218,9 @@ __device__ __forceinline__ float4 gg_bf4(const unsigned short *p) {         // 8
 // h / s tiles of EPI_DACT, the bias) is 16 bytes per lane and 256 contiguous bytes per row,
 // and a row dot is a 16-lane DPP reduction.  The caller has synchronised the workgroup: the
 // operand tiles in `smem` are dead.
-// (BF16: bias, out, out2, h_in and s_in hold bf16; the pdot rows are fp32 and optional)
-template <int NI, int EPI, bool BF16 = false>
+// (BF16: bias, out, out2, h_in and s_in hold bf16; the pdot rows are fp32 and optional.  HALVES: `w` may
+// hold halves -- the image path's fp32 kernels; the register path never sees such a weight)
+template <int NI, int EPI, bool BF16 = false, bool HALVES = !BF16>
 __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
                                             f32x16 (&acc)[NI][2], int bucket, int row_lo,
                                             int row_hi, int col_tile, int wm, int wn,
@@ -344,7 +369,7 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
                     const int owner = __ffsll(todo) - 1;
                     const unsigned m = __shfl(cand, owner, 64);
                     const int e = __ffs(m) - 1;
-                    const float exact = gg_exact_preact(g, bucket, __shfl(p, owner, 64),
+                    const float exact = gg_exact_preact<false, HALVES>(g, bucket, __shfl(p, owner, 64),
                                                         __shfl(n, owner, 64) + e, lane);
                     if (lane == owner) {
 #pragma unroll
@@ -421,6 +446,12 @@ __device__ __forceinline__ void gg_epilogue(const GroupedArgs &g, float *smem,
             }
         }
     }
+}
+
+// K in segments, or a second term wider than one k-step or in 16-column segments: the forms only the
+// register path takes -- and, for a weight stored in halves, the image path's segmented kernel
+__host__ __device__ inline bool gg_segmented(const GroupedArgs &g) {
+    return g.a_seg_k > 0 || (g.a2 && (g.R > GG_BK || g.b2_seg != 0));
 }
 
 struct GgWork {

@@ -45,7 +45,7 @@
 // The units (grouped_gemm.h: what they share, and the launchers this file calls):
 //   grouped_gemm.hip        this file: the C entries, validation and choice of the path
 //                           (launch_grouped, launch_grouped_bf16), and the kernels beside the GEMM:
-//                           split_bf16_kernel, relu_fix_kernel, rows_combine(_bf16)_kernel
+//                           split_bf16_kernel, split_f16_kernel, relu_fix_kernel, rows_combine(_bf16)_kernel
 //   grouped_gemm_img.hip    the IMAGE path (fp32 semantics and bf16 tensors)
 //   grouped_gemm_ring.hip   the image path as a loader / consumer ring (opt-in, SPT_GEMM_RING=1)
 //   grouped_gemm_regs.hip   the REGISTER path
@@ -78,6 +78,36 @@ __global__ __launch_bounds__(256) void split_bf16_kernel(const float *__restrict
     } else {
 #pragma unroll
         for (int e = 0; e < 8; e++) x[e] = col + e < cols ? p[e] : 0.0f;
+    }
+    const Frag f = split8(x);
+    char *dst = img + (chunk_row * 128) + c * 16;
+    *reinterpret_cast<uint4 *>(dst) = f.hi;
+    *reinterpret_cast<uint4 *>(dst + 64) = f.lo;
+}
+
+// The same image from IEEE halves [rows, cols] (spt_split_f16): a thread's 8 columns are ONE 16-byte
+// load, widened (exact: every half is an fp32 value) and split as above -- byte for byte the image
+// of the fp32 upcast, read from half the bytes.
+__global__ __launch_bounds__(256) void split_f16_kernel(const _Float16 *__restrict__ src,
+                                                        char *__restrict__ img, long long rows,
+                                                        int cols, long long ld, int blocks) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long chunk_row = idx >> 2;               // (row, block)
+    const int c = (int)(idx & 3);
+    const long long row = chunk_row / blocks;
+    const int kb = (int)(chunk_row - row * blocks);
+    if (row >= rows) return;
+    const int col = kb * 32 + c * 8;
+    const _Float16 *p = src + row * ld + col;
+    float x[8];
+    if (col + 8 <= cols) {
+        const h8 v = *reinterpret_cast<const h8 *>(p);
+#pragma unroll
+        for (int e = 0; e < 8; e++) x[e] = (float)v[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; e++) x[e] = col + e < cols ? (float)p[e] : 0.0f;
     }
     const Frag f = split8(x);
     char *dst = img + (chunk_row * 128) + c * 16;
@@ -180,7 +210,10 @@ static int resident_slots() {
 // image, the activation as its fp32 rows (16-byte aligned, lda % 4 == 0: one LDS-DMA lane moves 16 bytes)
 static int image_path(GroupedArgs &g, int epilogue) {
     if (!g.w_img || (!g.a_img && !g.a)) return 0;
-    if (g.K % GG_BK != 0 || g.a_seg_k > 0 || (g.a2 && (g.R > GG_BK || g.b2_seg != 0))) return 0;
+    if (g.K % GG_BK != 0) return 0;
+    // (segments and a wide second term: the register path's -- but for a weight in halves, which runs them
+    // from its image and the activation's fp32 rows: grouped_gemm_img.hip, the segmented kernel)
+    if (gg_segmented(g) && (!g.w_f16 || g.a_img || epilogue != EPI_PLAIN)) return 0;
     const long long row_len = g.ldk == 1 ? g.ldn : g.ldk;       // elements of one weight row
     if (row_len <= 0 || g.gstride % 32 != 0 || row_len % 32 != 0) return 0;
     g.w_grow = g.gstride / row_len;
@@ -225,7 +258,7 @@ static int launch_grouped(GroupedArgs g, int epilogue, void *stream) {
     const unsigned col_tiles = (unsigned)((g.N + GG_BN - 1) / GG_BN);
     if ((unsigned long long)row_tiles * col_tiles > 0x3FFFFFFFull) return SPT_EUNSUP;
     if (epilogue == EPI_ACT && g.act == ACT_RELU) {
-        // the near-the-kink recomputation reads the fp32 operands
+        // the near-the-kink recomputation reads the operands themselves (w_f16: the weight's halves)
         if (!g.a_norm || !g.w_norm || !g.a || !g.w) return SPT_EINVAL;
     }
     if (epilogue == EPI_DACT) {
@@ -240,11 +273,12 @@ static int launch_grouped(GroupedArgs g, int epilogue, void *stream) {
     if (g.slots <= 0) return SPT_EINVAL;
     const int img = image_path(g, epilogue);
     if (!img && (!g.a || !g.w)) return SPT_EUNSUP;              // images only, but not usable
+    if (!img && g.w_f16) return SPT_EUNSUP;                     // no register-operand form of halves
     // the loader / consumer ring (grouped_gemm_ring.hip, which says why it is opt-in): plain epilogue, image
     // path, nothing to add into; one workgroup per CU (read at every call: tests switch it inside one process)
     const char *ring_env = getenv("SPT_GEMM_RING");
     const bool ring_on = ring_env && ring_env[0] == '1';
-    if (img && epilogue == EPI_PLAIN && !g.accumulate && ring_on && (g.slots % 16) == 0 &&
+    if (img && epilogue == EPI_PLAIN && !g.accumulate && ring_on && !g.w_f16 && (g.slots % 16) == 0 &&
         (long long)GR_BM * g.ldo * 4 < 0x7fffffffLL && (!ext || g.R <= GG_BK))
         return launch_gemm_ring(g, ext, img == GG_OPS_A32, dim3(g.slots / GG_SLOTS_PER_CU), s);
     const bool k_tail = (g.K % GG_BK) != 0;
@@ -280,8 +314,7 @@ extern "C" int spt_grouped_gemm(const float *a, const int32_t *gather, const flo
 
 extern "C" int spt_grouped_gemm_pdot_width(int n) { return n > 0 ? 2 * ((n + GG_BN - 1) / GG_BN) : 0; }
 
-extern "C" int spt_grouped_gemm_fused(const SptGroupedGemm *d, void *stream) {
-    if (!d) return SPT_EINVAL;
+static GroupedArgs args_of(const SptGroupedGemm *d) {
     GroupedArgs g = {};
     g.a = d->a; g.gather = d->gather; g.w = d->w; g.bias = d->bias; g.rowscale = d->rowscale;
     g.offsets = d->offsets; g.out = d->out;
@@ -305,12 +338,30 @@ extern "C" int spt_grouped_gemm_fused(const SptGroupedGemm *d, void *stream) {
         const long long cap = (d->relu_queue_bytes - header) / 8 / GG_FIX_SEGS;
         g.fix_cap = (int)(cap > 0x7FFFFF ? 0x7FFFFF : cap);
     }
+    return g;
+}
+
+extern "C" int spt_grouped_gemm_fused(const SptGroupedGemm *d, void *stream) {
+    if (!d) return SPT_EINVAL;
+    return launch_grouped(args_of(d), d->epilogue, stream);
+}
+
+// `w` as IEEE halves: the k-loop kernels of the image path as they are (they read w_image alone); the
+// recomputation in front of a ReLU widens the halves it loads.  Always the default kernels.
+extern "C" int spt_grouped_gemm_fused_w16(const SptGroupedGemm *d, void *stream) {
+    if (!d) return SPT_EINVAL;
+    if ((!d->a && !d->a_image) || !d->w || !d->offsets || !d->out) return SPT_EINVAL;
+    if (!d->w_image) return SPT_EUNSUP;
+    if ((reinterpret_cast<uintptr_t>(d->w) & 7) != 0) return SPT_ESHAPE;      // four halves per load
+    GroupedArgs g = args_of(d);
+    g.w_f16 = 1;
     return launch_grouped(g, d->epilogue, stream);
 }
 
-extern "C" int spt_grouped_gemm_image_path(const SptGroupedGemm *d) {
+static int image_path_of(const SptGroupedGemm *d, int w_f16) {
     if (!d) return 0;
     GroupedArgs g = {};
+    g.w_f16 = w_f16;
     g.K = d->k; g.gstride = d->w_group_stride; g.ldn = d->w_ldn; g.ldk = d->w_ldk;
     g.act = d->activation;
     g.a = d->a; g.lda = d->lda;
@@ -318,6 +369,13 @@ extern "C" int spt_grouped_gemm_image_path(const SptGroupedGemm *d) {
     g.a_img = reinterpret_cast<const char *>(d->a_image);
     g.w_img = reinterpret_cast<const char *>(d->w_image);
     return image_path(g, d->epilogue);
+}
+
+extern "C" int spt_grouped_gemm_image_path(const SptGroupedGemm *d) { return image_path_of(d, 0); }
+
+// ... of spt_grouped_gemm_fused_w16: the one place that says which forms halves admit (image_path)
+extern "C" int spt_grouped_gemm_image_path_w16(const SptGroupedGemm *d) {
+    return image_path_of(d, 1);
 }
 
 extern "C" size_t spt_split_bf16_bytes(long long rows, int cols) {
@@ -338,6 +396,23 @@ extern "C" int spt_split_bf16(const float *src, void *image, long long rows, int
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, src, reinterpret_cast<char *>(image), rows, cols, ld,
                        blocks);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
+
+extern "C" int spt_split_f16(const void *src_f16, void *image, long long rows, int cols, long long ld,
+                             void *stream) {
+    if (!src_f16 || !image) return SPT_EINVAL;
+    if (rows <= 0 || cols <= 0 || ld < cols) return SPT_EINVAL;
+    if (ld % 8 != 0 || (reinterpret_cast<uintptr_t>(src_f16) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(image) & 15) != 0)
+        return SPT_ESHAPE;
+    const int blocks = (cols + 31) / 32;
+    const long long threads = rows * blocks * 4;
+    if ((threads + 255) / 256 > 0x7FFFFFFFll) return SPT_EUNSUP;
+    hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, static_cast<const _Float16 *>(src_f16),
+                       reinterpret_cast<char *>(image), rows, cols, ld, blocks);
     SPT_LAUNCH_CHECK();
     return SPT_OK;
 }

@@ -154,10 +154,14 @@ __device__ __forceinline__ void gi_step(const GiLane<NI, NA> &c, char *__restric
 // carry bf16 tensors); both operands go global -> LDS by LDS-DMA straight from the tensors, 64 k per
 // stage in the tiles' 128-byte rows (KC: chunk c = k 8 c .. 8 c + 7; NC: "part" 0 / 1 = k-rows
 // kr / 32 + kr of the step), two plain MFMAs per fragment pair; no K extension
-template <int BM, bool BN_LAYOUT, int EPI, bool EXT, bool A32, bool BF16 = false>
+// SEG (spt_grouped_gemm_fused_w16 alone): the segmented contraction of the register path (a_seg_k,
+// R up to 64, b2_seg) from the weight's image and the activation's fp32 rows -- the same k-steps in the
+// same order, so the same bits -- for a weight stored in halves, which has no register-operand form
+template <int BM, bool BN_LAYOUT, int EPI, bool EXT, bool A32, bool BF16 = false, bool SEG = false>
 __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem, int bucket,
                                               int row_lo, int row_hi, int col_tile) {
     static_assert(!(BF16 && A32), "bf16: no fp32 rows");
+    static_assert(!SEG || (A32 && EPI == EPI_PLAIN), "segments: fp32 rows, plain epilogue");
     constexpr int NI = BM / 64;                 // 32-row sub-blocks per wave
     constexpr int NA = BM / 32;                 // LDS-DMA instructions per wave: A tile
     constexpr int KS = BF16 ? 2 * GG_BK : GG_BK;    // k per stage
@@ -254,13 +258,39 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
 #define GG_ST
 #define GG_BAR(x) __syncthreads()
 #endif
-    for (int k0 = 0; k0 < g.K; k0 += 2 * KS) {
-        gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0 + GI_STAGE, lds0, k0 + KS < g.K, k0 + KS, acc GG_ST);
-        GG_BAR(0);
-        if (k0 + KS < g.K) {
-            gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0, lds0 + GI_STAGE, k0 + 2 * KS < g.K,
-                                                  k0 + 2 * KS, acc GG_ST);
+    if constexpr (SEG) {
+        // K in segments: gi_stage reads a_src + 4 k0 bytes, so when the NEXT step to be staged opens a
+        // new segment the sources move on by what lies between the two matrices (the register path's a_adj)
+        const long long seg_skip = (g.a_seg_stride - g.a_seg_k) * 4;
+        int seg_left = g.a_seg_k > 0 ? g.a_seg_k - KS : 0x7FFFFFFF;      // (step 0 is staged)
+        auto next_step = [&]() {
+            if (seg_left <= 0) {
+#pragma unroll
+                for (int j = 0; j < NA; j++) c.a_src[j] += seg_skip;
+                seg_left = g.a_seg_k;
+            }
+            seg_left -= KS;
+        };
+        for (int k0 = 0; k0 < g.K; k0 += 2 * KS) {
+            next_step();
+            gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0 + GI_STAGE, lds0, k0 + KS < g.K, k0 + KS, acc GG_ST);
             GG_BAR(0);
+            if (k0 + KS < g.K) {
+                next_step();
+                gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0, lds0 + GI_STAGE, k0 + 2 * KS < g.K,
+                                                      k0 + 2 * KS, acc GG_ST);
+                GG_BAR(0);
+            }
+        }
+    } else {
+        for (int k0 = 0; k0 < g.K; k0 += 2 * KS) {
+            gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0 + GI_STAGE, lds0, k0 + KS < g.K, k0 + KS, acc GG_ST);
+            GG_BAR(0);
+            if (k0 + KS < g.K) {
+                gi_step<NI, NA, BN_LAYOUT, A32, BF16>(c, lds0, lds0 + GI_STAGE, k0 + 2 * KS < g.K,
+                                                      k0 + 2 * KS, acc GG_ST);
+                GG_BAR(0);
+            }
         }
     }
 #ifdef GG_STAMP_DMA
@@ -310,6 +340,46 @@ __device__ __forceinline__ void gemm_tile_img(const GroupedArgs &g, float *smem,
         gi_contract<NI, NA, true, true>(c, As, Bs, 0, acc);
         if (g.R > 16) gi_contract<NI, NA, true, true>(c, As, Bs, 1, acc);
         __syncthreads();
+    } else if constexpr (EXT && SEG) {
+        // up to 64 columns, 32 per step as on the register path; b2 possibly in 16-column segments
+        char *As = lds0, *Bs = lds0 + GI_TILE;
+        const int kq = tid & 7;
+        auto put4 = [&](char *tile, int r, const float4 &v) {
+            const Split s0 = split2(v.x, v.y), s1 = split2(v.z, v.w);
+            const int sw = (r >> 1) & 7;
+            char *row = tile + r * 128 + (kq & 1) * 8;
+            *reinterpret_cast<uint2 *>(row + (((kq >> 1) ^ sw) << 4)) = make_uint2(s0.hi, s1.hi);
+            *reinterpret_cast<uint2 *>(row + (((4 + (kq >> 1)) ^ sw) << 4)) = make_uint2(s0.lo, s1.lo);
+        };
+        for (int r0 = 0; r0 < g.R; r0 += GG_BK) {
+            const int k = r0 + 4 * kq;
+#pragma unroll
+            for (int u = 0; u < BM / 32; u++) {
+                const int r = (tid >> 3) + 32 * u;
+                const int p = row_lo + r;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (p < row_hi && k < g.R) {
+                    const long long src = g.gather2 ? g.gather2[p] : p;
+                    v = *reinterpret_cast<const float4 *>(g.a2 + src * g.lda2 + k);
+                }
+                put4(As, r, v);
+            }
+#pragma unroll
+            for (int u = 0; u < GG_BN / 32; u++) {
+                const int r = (tid >> 3) + 32 * u;
+                const int n = n0 + r;
+                float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (n < g.N && k < g.R)
+                    b = *reinterpret_cast<const float4 *>(
+                        g.b2 + (size_t)bucket * g.b2_gstride + (size_t)n * g.b2_ldn +
+                        (g.b2_seg ? (size_t)(k >> 4) * g.b2_seg + (k & 15) : (size_t)k));
+                put4(Bs, r, b);
+            }
+            __syncthreads();
+            gi_contract<NI, NA, true>(c, As, Bs, 0, acc);
+            if (g.R - r0 > 16) gi_contract<NI, NA, true>(c, As, Bs, 1, acc);
+            __syncthreads();
+        }
     } else if (EXT) {
         char *As = lds0, *Bs = lds0 + GI_TILE;
         const int kq = tid & 7, k = 4 * kq;                 // 8 lanes per row: 4 k's each
@@ -390,6 +460,20 @@ __global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_img_kernel(Grouped
                                                            w.col_tile);
 }
 
+// the segmented form (gemm_tile_img: SEG): plain epilogue, the activation's fp32 rows
+template <bool BN_LAYOUT, bool EXT>
+__global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_img_seg_kernel(GroupedArgs g) {
+    __shared__ __attribute__((aligned(1024))) float smem[GI_LDS_FLOATS + GG_EXTRAS];
+    const GgWork w = gg_find_work(g);
+    if (w.bucket < 0) return;
+    if (w.half < 0)
+        gemm_tile_img<GG_BM, BN_LAYOUT, EPI_PLAIN, EXT, true, false, true>(g, smem, w.bucket, w.row_lo, w.row_hi,
+                                                                           w.col_tile);
+    else
+        gemm_tile_img<GG_BM / 2, BN_LAYOUT, EPI_PLAIN, EXT, true, false, true>(g, smem, w.bucket, w.row_lo,
+                                                                               w.row_hi, w.col_tile);
+}
+
 // spt_grouped_gemm_bf16: the image kernel's k-loop and epilogue on bf16 tensors (PLAIN / ACT / DACT)
 template <bool BN_LAYOUT, int EPI>
 __global__ __launch_bounds__(GG_THREADS, 2) void grouped_gemm_bf16_kernel(GroupedArgs g) {
@@ -434,7 +518,12 @@ static GgKernel img_kernel(int epilogue, bool ext, int operands) {
 }
 
 int launch_gemm_img(const GroupedArgs &g, int epilogue, bool ext, int operands, dim3 grid, hipStream_t s) {
-    const GgKernel kernel = g.ldk == 1 ? img_kernel<false>(epilogue, ext, operands) : img_kernel<true>(epilogue, ext, operands);
+    GgKernel kernel = g.ldk == 1 ? img_kernel<false>(epilogue, ext, operands) : img_kernel<true>(epilogue, ext, operands);
+    if (operands == GG_OPS_A32 && gg_segmented(g)) {
+        if (epilogue != EPI_PLAIN) return SPT_EUNSUP;
+        kernel = g.ldk == 1 ? (ext ? grouped_gemm_img_seg_kernel<false, true> : grouped_gemm_img_seg_kernel<false, false>)
+                            : (ext ? grouped_gemm_img_seg_kernel<true, true> : grouped_gemm_img_seg_kernel<true, false>);
+    }
     hipLaunchKernelGGL(kernel, grid, dim3(GG_THREADS), 0, s, g);
     SPT_LAUNCH_CHECK();
     return SPT_OK;

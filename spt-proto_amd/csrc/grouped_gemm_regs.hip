@@ -238,7 +238,7 @@ __device__ __forceinline__ void gemm_tile_regs(const GroupedArgs &g, float *smem
         }
     }
     __syncthreads();   // all waves are done with the operand tiles
-    gg_epilogue<NI, EPI>(g, smem, acc, bucket, row_lo, row_hi, col_tile, wm, wn, extras, EXT);
+    gg_epilogue<NI, EPI, false, false>(g, smem, acc, bucket, row_lo, row_hi, col_tile, wm, wn, extras, EXT);
 }
 
 template <bool BN_LAYOUT, int EPI, bool EXT, bool KTAIL>

@@ -75,6 +75,8 @@ _PROTOTYPES = {
     'spt_grouped_gemm_fused': ([_c_ptr, _c_ptr], _c_int),
     'spt_grouped_gemm_pdot_width': ([_c_int], _c_int),
     'spt_grouped_gemm_image_path': ([_c_ptr], _c_int),
+    'spt_grouped_gemm_image_path_w16': ([_c_ptr], _c_int),
+    'spt_grouped_gemm_fused_w16': ([_c_ptr, _c_ptr], _c_int),
     'spt_grouped_gemm_wgrad_workspace_bytes': ([ctypes.c_longlong, _c_int, _c_int, _c_int], ctypes.c_longlong),
     'spt_grouped_gemm_wgrad': ([_c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr, ctypes.c_longlong] + [_c_ptr] * 3
                                + [_c_int, ctypes.c_longlong, _c_int, _c_int, _c_ptr, ctypes.c_longlong,
@@ -95,6 +97,7 @@ _PROTOTYPES = {
                                        ctypes.c_longlong] + [_c_ptr] * 3, _c_int),
     'spt_split_bf16_bytes': ([ctypes.c_longlong, _c_int], ctypes.c_size_t),
     'spt_split_bf16': ([_c_ptr, _c_ptr, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_ptr], _c_int),
+    'spt_split_f16': ([_c_ptr, _c_ptr, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_ptr], _c_int),
     'spt_rotary': ([_c_ptr, _c_int, _c_int, _c_ptr, ctypes.c_longlong, _c_ptr, _c_ptr] + [_c_int] * 5 + [_c_ptr],
                    _c_int),
     'spt_swiglu_forward': ([_c_ptr] * 3 + [ctypes.c_longlong, _c_ptr], _c_int),
@@ -181,8 +184,16 @@ def paths_taken(site: str = None) -> dict:
     return {k: v for k, v in PATH_COUNTS.items() if site is None or k[0] == site}
 
 
-def reset_paths() -> None:
+def reset_paths(reasons: bool = False) -> None:
+    """Forget the counts; `reasons`: the logged fallback reasons too (each is then logged once more)."""
     PATH_COUNTS.clear()
+    if reasons:
+        _PATH_LOGGED.clear()
+
+
+def fallback_reasons(site: str, path: str) -> list:
+    """The reasons logged for `site` leaving its primary path for `path` (a few per site are kept)."""
+    return sorted(k[2] for k in _PATH_LOGGED if k[:2] == (site, path))
 
 
 def load_library() -> ctypes.CDLL:
@@ -1253,18 +1264,22 @@ class SplitImage:
 
 
 def split_bf16(x: torch.Tensor) -> SplitImage:
-    """fp32 [rows, cols] (unit inner stride) -> its hi / lo bf16 image, one launch."""
-    _check_type(x, torch.float32, 'x')
-    _require(x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0,
-             'split_bf16: CUDA fp32 matrix with unit inner stride and 16-byte aligned rows')
+    """fp32 [rows, cols] (unit inner stride) -> its hi / lo bf16 image, one launch.  A fp16 matrix (a
+    frozen weight stored in halves) gives, byte for byte, the image of its fp32 upcast (``spt_split_f16``)."""
+    f16 = x.dtype == torch.float16
+    if not f16:
+        _check_type(x, torch.float32, 'x')
+    _require(x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % (8 if f16 else 4) == 0
+             and x.data_ptr() % 16 == 0,
+             'split_bf16: CUDA fp32 (or fp16) matrix with unit inner stride and 16-byte aligned rows')
     rows, cols = x.shape
     lib = load_library()
     dev = x.device
     with _on(dev):
         buf = torch.empty([lib.spt_split_bf16_bytes(rows, cols)], dtype=torch.uint8, device=dev)
         if rows > 0:
-            rc = lib.spt_split_bf16(x.data_ptr(), buf.data_ptr(), rows, cols, x.stride(0),
-                                    _stream(dev))
+            rc = (lib.spt_split_f16 if f16 else lib.spt_split_bf16)(x.data_ptr(), buf.data_ptr(), rows, cols,
+                                                                    x.stride(0), _stream(dev))
             if rc != 0:
                 _raise(lib, rc, 'split_bf16')
     return SplitImage(buf, rows, cols)
@@ -1377,8 +1392,9 @@ KEEP_WEIGHT_IMAGES = os.environ.get('SPT_WEIGHT_IMAGES', 'step') == 'keep'
 
 
 def row_norms(x: torch.Tensor) -> torch.Tensor:
-    """Euclidean norm of every row of a matrix (fp32 [rows])."""
-    return torch.linalg.vector_norm(x.detach(), dim=1)
+    """Euclidean norm of every row of a matrix (fp32 [rows]).  Of a fp16-stored weight: of its fp32
+    upcast (transient), by the same call -- the same norms, so the same near-the-kink cells."""
+    return torch.linalg.vector_norm(x.detach().float(), dim=1)
 
 
 _WEIGHT_NORMS = _PerParameter()
@@ -1426,9 +1442,18 @@ def grouped_gemm_fused(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Ten
     ``accumulate`` the product is ADDED to what `out` holds.  ``a_segments`` = (seg_k, seg_stride):
     `a` is the first of k / seg_k matrices [rows, seg_k] that lie seg_stride floats apart (the
     caller vouches for the others' memory), contracted one after the other.  ``b2_segment_stride``:
-    `b2` [n, 16] is the first of a2.size(1) / 16 such tables lying that many floats apart."""
-    for t, name in ((a, 'a'), (weight, 'weight')):
-        _check_type(t, torch.float32, name)
+    `b2` [n, 16] is the first of a2.size(1) / 16 such tables lying that many floats apart.
+    ``weight`` may be fp16 (a frozen weight stored in halves): ``spt_grouped_gemm_fused_w16`` then runs
+    from ``w_image`` (mandatory; the image path must apply) to the bits of the fp32 upcast -- ``a_segments``
+    included, which a fp32 weight runs through registers and halves from the image and the fp32 rows of `a`."""
+    _check_type(a, torch.float32, 'a')
+    # a fp16 `weight` (a frozen weight stored in halves, every value of which is an fp32 value): run
+    # from its image alone, to the bits of the fp32 upcast (spt_grouped_gemm_fused_w16); never upcast here
+    w16 = weight.dtype == torch.float16
+    if not w16:
+        _check_type(weight, torch.float32, 'weight')
+    _require(not w16 or w_image is not None,
+             'grouped_gemm_fused: a fp16 weight runs on the image path only and needs `w_image`')
     _check_type(offsets, torch.int32, 'offsets')
     _require(a.dim() == 2 and a.stride(1) == 1, 'a must be [rows, k] with unit inner stride')
     _require(weight.is_contiguous(), 'weight must be contiguous')
@@ -1449,7 +1474,7 @@ def grouped_gemm_fused(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Ten
             a_norm = row_norms(a)
         if w_norm is None:          # |W_g(n, :)| for every (g, n): rows, or columns when n runs fastest
             w_norm = row_norms(weight.view(-1, w_ldn)) if w_ldk == 1 else \
-                torch.linalg.vector_norm(weight.view(-1, w_ldk), dim=0)
+                torch.linalg.vector_norm(weight.float().view(-1, w_ldk), dim=0)
         for t, rows, name in ((a_norm, a.size(0), 'a_norm'), (w_norm, n_groups * n, 'w_norm')):
             _check_type(t, torch.float32, name)
             _require(t.is_cuda and t.is_contiguous() and t.numel() == rows,
@@ -1512,10 +1537,18 @@ def grouped_gemm_fused(a: torch.Tensor, weight: torch.Tensor, offsets: torch.Ten
                 a_seg_stride=a_segments[1] if a_segments else 0,
                 b2_seg_stride=b2_segment_stride)
             global LAST_GEMM_USED_IMAGES, LAST_GEMM_PATH
-            LAST_GEMM_PATH = ('register', 'image', 'a32')[lib.spt_grouped_gemm_image_path(ctypes.byref(desc))]
+            # (halves: the library's own answer for its _w16 entry, which alone takes segments from the image)
+            form = (lib.spt_grouped_gemm_image_path_w16 if w16 else lib.spt_grouped_gemm_image_path)(
+                ctypes.byref(desc))
+            _require(form != 0 or not w16,
+                     'grouped_gemm_fused: a fp16 weight runs on the image path only, which does not take this '
+                     'call (k % 32 == 0, weight rows and group stride multiples of 32, r <= 32 or the plain '
+                     'epilogue, a 16-byte aligned with a row stride % 4 == 0)')
+            LAST_GEMM_PATH = ('register', 'image', 'a32')[form]
             LAST_GEMM_USED_IMAGES = LAST_GEMM_PATH != 'register'
             PATH_COUNTS[('grouped_gemm', LAST_GEMM_PATH)] += 1
-            rc = lib.spt_grouped_gemm_fused(ctypes.byref(desc), _stream(dev))
+            rc = (lib.spt_grouped_gemm_fused_w16 if w16 else lib.spt_grouped_gemm_fused)(ctypes.byref(desc),
+                                                                                         _stream(dev))
             if rc != 0:
                 _raise(lib, rc, 'grouped_gemm_fused')
     if epilogue == EPI_ACT:

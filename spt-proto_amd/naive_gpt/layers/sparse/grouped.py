@@ -380,6 +380,26 @@ def usable(x: torch.Tensor, *frozen_weights) -> bool:
     return True
 
 
+def f16_unusable(x: torch.Tensor, rank: int, fused: bool, d: int, bs: int):
+    """Block weights stored in halves (utils.tuning.store_frozen_fp16) run from their images alone, which
+    the FUSED grouped path with whole 32-element blocks provides: None when this call is such a one, else
+    the reason it is not (the layer then upcasts the weights for the call and notes the fallback)."""
+    if not x.is_cuda:
+        return 'x on {}'.format(x.device)
+    if not fused:
+        return 'the fused grouped path does not take this layer (activation, rank {}, router, fc2.bias)'.format(rank)
+    if d % 32 != 0 or bs % 32 != 0:
+        return 'd_model {} / block size {}: the image path takes multiples of 32'.format(d, bs)
+    return None
+
+
+def _w_image(w: torch.Tensor, imgs: bool):
+    """The weight's image where the call runs from images -- always, for a weight stored in halves (the
+    GEMMs that read a fp32 weight through registers read a fp16 one from its image: the same MFMAs on
+    the same fragments in the same order)."""
+    return ext.weight_image(w) if imgs or w.dtype == torch.float16 else None
+
+
 def bf16_usable(x: torch.Tensor, *frozen_weights) -> bool:
     """The bf16 grouped path of the PLAIN routed FFNs (feedforward.py; the LoRA routed variants have their
     own, lora_bf16_usable): bf16 CUDA activations and frozen bf16 base weights, every one of them."""
@@ -729,7 +749,7 @@ class RoutedLoRAFFN(torch.autograd.Function):
             n_rows=rows, gather=bk.token, bias=b1, rowscale=coeff,
             a2=u, gather2=bk.token, b2=r1, b2_group_stride=bs * rank,
             epilogue=ext.EPI_ACT, activation=act, keep_preact=not relu,
-            a_image=x_img, w_image=ext.weight_image(w1) if imgs else None,
+            a_image=x_img, w_image=_w_image(w1, imgs),
             a_norm=x_norm, w_norm=ext.weight_row_norms(w1) if relu else None)
         # (h has ONE reader: no image of it -- the GEMM splits its fp32 rows itself ("A32", +11 us)
         # and the down product runs without the image store (-20 us))
@@ -737,7 +757,7 @@ class RoutedLoRAFFN(torch.autograd.Function):
         ys = ext.grouped_gemm_fused(
             h, w2, bk.offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1,
             n_rows=rows, rowscale=coeff, a2=z, b2=r2, b2_group_stride=0,
-            a_image=h_img, w_image=ext.weight_image(w2) if imgs else None)
+            a_image=h_img, w_image=_w_image(w2, imgs))
         y = ext.rows_combine(ys, bk.pos, bias=b2)
         ctx.bk, ctx.act = bk, act
         # x is a norm output the block can recompute: keep its origin instead (tuning/recompute.py)
@@ -768,7 +788,7 @@ class RoutedLoRAFFN(torch.autograd.Function):
             n_rows=rows, gather=bk.token, rowscale=coeff,
             a2=dzt, gather2=bk.token, b2=l2, b2_group_stride=bs * rank,
             epilogue=ext.EPI_DACT, activation=act, h_in=h, s_in=s,
-            a_image=dy_img, w_image=ext.weight_image(w2) if imgs else None, raw_dots=True)
+            a_image=dy_img, w_image=_w_image(w2, imgs), raw_dots=True)
         du, _ = _down_blocks(ds, r1, bk, False)                              # [P, r]
         # d/dc = <dy W2_g^T, h> + <ds, x W1_g^T + b1_g>.  The kernel's dot_main = <v, h> with
         # v = c (dy W2_g^T) + dzt L2_g^T (the value before act'), dot_act = <ds, s> with
@@ -821,7 +841,7 @@ class RoutedLoRAFFN(torch.autograd.Function):
         del dot_main, dot_act, du_tok, dzt
         dxs = ext.grouped_gemm_fused(
             ds, w1, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
-            n_rows=rows, rowscale=coeff, a2=du, b2=l1, b2_group_stride=0)
+            n_rows=rows, rowscale=coeff, a2=du, b2=l1, b2_group_stride=0, w_image=_w_image(w1, False))
         del ds, du
         if router_rides:
             # the router's share d logit . W_r of grad_x inside the un-bucketing pass
@@ -899,7 +919,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
                 x, w, bk.offsets, nb, n=bs, k=d, w_group_stride=bs * d, w_ldn=d, w_ldk=1,
                 n_rows=rows, gather=bk.token, rowscale=coeff, a2=u, gather2=bk.token,
                 b2=r_table, b2_group_stride=bs * rank,
-                a_image=x_image, w_image=ext.weight_image(w) if imgs else None)
+                a_image=x_image, w_image=_w_image(w, imgs))
 
         g, sd = up(wg, ug, rg), up(ws, us, rs)
         silu = isinstance(activation, torch.nn.SiLU) and ext.swiglu_supported(g, sd)
@@ -911,7 +931,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
         ys = ext.grouped_gemm_fused(
             h, wd, bk.offsets, nb, n=d, k=bs, w_group_stride=bs, w_ldn=d_ff, w_ldk=1,
             n_rows=rows, rowscale=coeff, a2=z, b2=rd, b2_group_stride=0,
-            a_image=h_img, w_image=ext.weight_image(wd) if imgs else None)
+            a_image=h_img, w_image=_w_image(wd, imgs))
         del x_image, h_img
         y = ext.rows_combine(ys, bk.pos)
         ctx.bk, ctx.activation = bk, activation
@@ -942,7 +962,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
             dy, wd, bk.offsets, nb, n=bs, k=d, w_group_stride=bs, w_ldn=1, w_ldk=d_ff,
             n_rows=rows, gather=bk.token, rowscale=coeff, a2=dzt, gather2=bk.token, b2=ld,
             b2_group_stride=bs * rank,
-            a_image=dy_img, w_image=ext.weight_image(wd) if imgs else None)
+            a_image=dy_img, w_image=_w_image(wd, imgs))
         del dy_img
         silu = isinstance(activation, torch.nn.SiLU) and ext.swiglu_supported(g, sd)
         if silu:
@@ -971,7 +991,7 @@ class RoutedLoRALLaMAFFN(torch.autograd.Function):
             dxs = ext.grouped_gemm_fused(
                 dpre, w, bk.offsets, nb, n=d, k=bs, w_group_stride=bs * d, w_ldn=1, w_ldk=d,
                 n_rows=rows, rowscale=coeff, a2=du, b2=l_table, b2_group_stride=0,
-                out=into, accumulate=into is not None)
+                out=into, accumulate=into is not None, w_image=_w_image(w, False))
             grad_r = _tn_blocks(dpre, u, bk)
             return dxs, dc, ext.rows_combine(du, bk.pos), grad_r
 

@@ -105,6 +105,31 @@ def _one_group(rows: int, device) -> torch.Tensor:
     return off
 
 
+def _f16(weight: torch.Tensor) -> bool:
+    """A frozen base weight stored in halves (utils.tuning.store_frozen_fp16): every value is an fp32
+    value with at most 11 significant bits, its split image is that of its fp32 upcast, and the
+    matrix-core path runs from that image alone -- to the same bits as from fp32 storage."""
+    return weight.dtype == torch.float16
+
+
+def _f16_upcast(site: str, weight: torch.Tensor, why) -> torch.Tensor:
+    """The fp32 copy of ONE fp16-stored weight for ONE call that cannot run from its image (exact;
+    released with the call) -- noted as a fallback, never silent."""
+    from naive_gpt import ext
+    ext.note_path(site, 'f16_upcast', fallback=True,
+                  why=lambda: 'fp16-stored frozen weight {} upcast for this call: {}'.format(
+                      tuple(weight.shape), why() if callable(why) else why))
+    return weight.float()
+
+
+def _f16_refuse(x: torch.Tensor, weight: torch.Tensor) -> None:
+    if _f16(weight) and x.dtype != torch.float32:
+        raise RuntimeError(
+            'frozen weights stored in fp16 (store_frozen_fp16) serve fp32 modules only: the input is {}. '
+            'fp16 storage is exact under the fp32 split-bf16 arithmetic; a bf16 module '
+            '(.bfloat16(), SPT_ROUTED_LORA_BF16) rounds activations and is a different contract'.format(x.dtype))
+
+
 def _mfma_linear_usable(x2: torch.Tensor, weight: torch.Tensor, rank: int, forward: bool = True) -> bool:
     """Shapes for which the frozen product goes through the library's split-bf16 matrix-core
     GEMM (grouped_gemm.hip and its units, with one bucket; ~320 TFLOP/s against ~125 for the fp32 library
@@ -113,7 +138,9 @@ def _mfma_linear_usable(x2: torch.Tensor, weight: torch.Tensor, rank: int, forwa
     contracts over in_features, the backward (dX = dY W) over out_features -- a vocabulary of
     30522 takes the forward only."""
     n, k = weight.shape
-    return (x2.is_cuda and x2.dtype == torch.float32 and weight.dtype == torch.float32
+    if _f16(weight) and not (n % 32 == 0 and k % 32 == 0 and x2.data_ptr() % 16 == 0):
+        return False            # (halves run from the image only: whole 32-element blocks both ways)
+    return (x2.is_cuda and x2.dtype == torch.float32 and weight.dtype in (torch.float32, torch.float16)
             and x2.is_contiguous() and weight.is_contiguous() and x2.size(0) >= 2048
             and k % 4 == 0 and (forward or n % 4 == 0) and 0 < rank <= 32)
 
@@ -128,7 +155,7 @@ def _mfma_gemm(a, weight, n, k, ldn, ldk, bias=None, a2=None, b2=None, images=Fa
     from naive_gpt import ext
     rows = a.size(0)
     a_image = w_image = None
-    if images and k % 32 == 0 and a.is_contiguous():
+    if (images or _f16(weight)) and k % 32 == 0 and a.is_contiguous():
         # the activation's image only when one exists already (another consumer of the same input
         # made it: lora_down's by-product, q / k / v); a lone consumer reads the fp32 rows
         # themselves -- the kernel's A32 form, ~10 % slower than from an image, whose making costs
@@ -224,18 +251,20 @@ class _FrozenLoRALinear(torch.autograd.Function):
         from naive_gpt import ext
         x2 = x.reshape(-1, x.size(-1))
         n, k = weight.shape
+        _f16_refuse(x, weight)
         ctx.mfma = _mfma_linear_usable(x2, weight, left.size(1))
-        ext.note_path('lora_linear', 'mfma' if ctx.mfma else 'library', fallback=not ctx.mfma,
-                      why=lambda: 'x {} {} contiguous={} W {}: the split-bf16 GEMM takes fp32, >= 2048 rows, '
-                          'k % 4 == 0, rank <= 32'.format(tuple(x2.shape), x2.dtype, x2.is_contiguous(),
-                                                          tuple(weight.shape)))
+
+        def why():
+            return ('x {} {} contiguous={} W {}: the split-bf16 GEMM takes fp32, >= 2048 rows, '
+                    'k % 4 == 0, rank <= 32'.format(tuple(x2.shape), x2.dtype, x2.is_contiguous(), tuple(weight.shape)))
+        ext.note_path('lora_linear', 'mfma' if ctx.mfma else 'library', fallback=not ctx.mfma, why=why)
         u = _down(x, x2, left, ctx.mfma and x2.is_contiguous())      # [T, r]
         if ctx.mfma:
             # one launch: base product, bias and the side product (the K extension) together
             y = _mfma_gemm(x2, weight, n, k, k, 1, bias=None if bias is None else bias.view(1, n),
                            a2=u.contiguous(), b2=right.contiguous(), images=True, owner=x)
         else:
-            y = nn.functional.linear(x2, weight, bias)
+            y = nn.functional.linear(x2, _f16_upcast('lora_linear', weight, why) if _f16(weight) else weight, bias)
             y.addmm_(u, right.t())
         # a tagged norm output is not kept: its origin is (layers/tuning/recompute.py)
         origin = recompute.origin_of(x)
@@ -256,15 +285,17 @@ class _FrozenLoRALinear(torch.autograd.Function):
             n, k = weight.shape
             from naive_gpt import ext
             mfma = ctx.mfma and dy2.is_contiguous() and _mfma_linear_usable(dy2, weight, left.size(1), False)
-            ext.note_path('lora_linear_backward', 'mfma' if mfma else 'library', fallback=not mfma,
-                          why=lambda: 'dy {} contiguous={} W {}'.format(tuple(dy2.shape), dy2.is_contiguous(),
-                                                                tuple(weight.shape)))
+
+            def why():
+                return 'dy {} contiguous={} W {}'.format(tuple(dy2.shape), dy2.is_contiguous(), tuple(weight.shape))
+            ext.note_path('lora_linear_backward', 'mfma' if mfma else 'library', fallback=not mfma, why=why)
             if mfma:
                 # dX = dY W + dU L^T: the weight read with n contiguous... W'(k', n) = W[n, k']
                 grad_x = _mfma_gemm(dy2, weight, k, n, 1, k, a2=du.contiguous(),
                                     b2=left.contiguous())
             else:
-                grad_x = torch.matmul(dy2, weight)
+                grad_x = torch.matmul(dy2, _f16_upcast('lora_linear_backward', weight, why) if _f16(weight)
+                                      else weight)
                 grad_x.addmm_(du, left.t())
             grad_x = grad_x.view(ctx.x_shape)
         grad_left, grad_right = tall_tn_many([(x2, du) if ctx.needs_input_grad[3] else None,
@@ -293,22 +324,33 @@ def _home3(tensors):
             t.data = home[g]
     refs = [weakref.ref(tensors[0], lambda _, k=key: _HOMES.pop(k, None))]
     refs += [weakref.ref(t) for t in tensors[1:]]
-    _HOMES[key] = (refs, tuple(t.data_ptr() for t in tensors), home)
+    _HOMES[key] = (refs, tuple(t.data_ptr() for t in tensors), home, home.view(-1, home.size(-1)))
     return home
 
 
-def _equal_spacing(mats) -> int:
-    """floats from each matrix to the next when the three [rows, n] fp32 matrices are contiguous,
-    disjoint and equally spaced in memory (views of one buffer), else 0"""
+def _homed_rows(tensors):
+    """The three homed matrices as ONE [3 n, k] matrix -- the same tensor object call after call, so that
+    what `ext` keeps per weight (its image under SPT_WEIGHT_IMAGES=keep) is found again -- or None when
+    `tensors` are not (or no longer) the views `_home3` made."""
+    hit = _HOMES.get(id(tensors[0]))
+    if hit is None or hit[1] != tuple(t.data_ptr() for t in tensors):
+        return None
+    return hit[3]
+
+
+def _equal_spacing(mats, dtype=torch.float32) -> int:
+    """elements from each matrix to the next when the three [rows, n] matrices of `dtype` are
+    contiguous, disjoint and equally spaced in memory (views of one buffer), else 0"""
     a, b, c = mats
-    if not all(m.is_contiguous() and m.dtype == torch.float32 and m.shape == a.shape for m in mats):
+    if not all(m.is_contiguous() and m.dtype == dtype and m.shape == a.shape for m in mats):
         return 0
+    item = a.element_size()
     step = b.data_ptr() - a.data_ptr()
-    if step < a.numel() * 4 or c.data_ptr() - b.data_ptr() != step or step % 16 != 0:
+    if step < a.numel() * item or c.data_ptr() - b.data_ptr() != step or step % 16 != 0:
         return 0
     if not (a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr() == c.untyped_storage().data_ptr()):
         return 0
-    return step // 4
+    return step // item
 
 
 def _qkv_index(rows: int, device):
@@ -359,7 +401,9 @@ class _FrozenLoRAQKV(torch.autograd.Function):
         # rotated copies at once, and a shared buffer would keep their memory alive with v)
         joint = 2 if v_apart else 3
         r = rights[0].size(1)
-        w_img = ext.weight_image(w3.view(3 * n, k))
+        # (halves: the persistent view, whose image is then made once under SPT_WEIGHT_IMAGES=keep and
+        # serves the backward's joint dX too; fp32 storage as before)
+        w_img = ext.weight_image(_homed_rows(weights) if _f16(w3) else w3.view(3 * n, k))
         r_step = ext.spacing_of(rights[:joint])
         out = ext.grouped_gemm_fused(
             x2, w3, offsets[:joint + 1], joint, n, k, n * k, k, 1, joint * rows, gather=gather[:joint * rows],
@@ -419,7 +463,8 @@ class _FrozenLoRAQKV(torch.autograd.Function):
         grad_x = None
         if ctx.needs_input_grad[0]:
             step = _equal_spacing(dy2) if len(live) == 3 and r == 16 else 0
-            if step and _equal_spacing(weights) == n * k:
+            w16 = _f16(weights[0])
+            if step and _equal_spacing(weights, weights[0].dtype) == n * k:
                 # dX = [dQ | dK | dV] [Wq; Wk; Wv] + [dU_q | dU_k | dU_v] [L_q | L_k | L_v]^T: ONE
                 # contraction over k = 3 n -- the three gradients lie `step` floats apart (the
                 # attention's backward writes them into one buffer) and the three weights are one
@@ -427,10 +472,15 @@ class _FrozenLoRAQKV(torch.autograd.Function):
                 # no read-add-write of dX between them
                 ext.note_path('qkv_dx', 'joint')
                 l_step = ext.spacing_of(lefts)
+                w3 = weights[0].as_strided((3 * n, k), (k, 1))
+                # (halves: the same contraction from the three weights' one image and the gradients' fp32
+                # rows -- spt_grouped_gemm_fused_w16's segmented kernel, to the bits of the register form)
                 grad_x = ext.grouped_gemm_fused(
-                    dy2[0], weights[0].as_strided((3 * n, k), (k, 1)), one, 1, k, 3 * n, 0, 1, k, rows, a2=du_cat,
+                    dy2[0], w3, one, 1, k, 3 * n, 0, 1, k, rows, a2=du_cat,
                     b2=lefts[0].detach() if l_step else torch.cat([t.detach() for t in lefts], dim=1),
-                    b2_segment_stride=l_step, a_segments=(n, step))
+                    b2_segment_stride=l_step, a_segments=(n, step),
+                    w_image=ext.weight_image(_homed_rows(weights) if _homed_rows(weights) is not None else w3)
+                    if w16 else None)
             else:
                 ext.note_path('qkv_dx', 'three_launches', fallback=len(live) == 3,
                               why=lambda: 'the gradients of q, k, v are not three equally spaced matrices '
@@ -441,7 +491,8 @@ class _FrozenLoRAQKV(torch.autograd.Function):
                     # dX (+)= dY_g W_g + dU_g L_g^T
                     grad_x = ext.grouped_gemm_fused(
                         dy2[g], weights[g], one, 1, k, n, 0, 1, k, rows, a2=dus[g],
-                        b2=lefts[g].contiguous(), out=grad_x, accumulate=grad_x is not None)
+                        b2=lefts[g].contiguous(), out=grad_x, accumulate=grad_x is not None,
+                        w_image=ext.weight_image(weights[g]) if w16 else None)
             if grad_x is not None:
                 grad_x = grad_x.view(ctx.x_shape)
         grad_lefts, grad_rights = [None] * 3, [None] * 3
@@ -473,7 +524,7 @@ def qkv_usable(x: torch.Tensor, linears) -> bool:
     if not all(isinstance(m, LoRALinear) and m._frozen() for m in linears):
         return False
     w = linears[0].weight
-    if any(m.weight.shape != w.shape or (m.bias is None) != (linears[0].bias is None)
+    if any(m.weight.shape != w.shape or m.weight.dtype != w.dtype or (m.bias is None) != (linears[0].bias is None)
            or m.lora.left.weight.size(1) != 16 for m in linears):
         return False
     x2 = x.reshape(-1, x.size(-1))
@@ -515,7 +566,14 @@ class LoRALinear(nn.Linear):
         if frozen and x.is_cuda and x.dim() >= 2:
             return _FrozenLoRALinear.apply(x, self.weight, self.bias,
                                            self.lora.left.weight, self.lora.right.weight)
-        y = nn.functional.linear(x, bias=self.bias, weight=self.weight)
+        _f16_refuse(x, self.weight)
+        weight = self.weight
+        if _f16(weight):
+            # (a fp16-stored weight off the frozen GPU path: its exact fp32 copy for this call, noted)
+            weight = _f16_upcast('lora_linear', weight, lambda: 'x {} on {}, frozen={}: the image path takes '
+                                 'CUDA inputs of two or more dimensions and a frozen bias'.format(
+                                     tuple(x.shape), x.device.type, frozen))
+        y = nn.functional.linear(x, bias=self.bias, weight=weight)
         y += torch.matmul(torch.matmul(x, self.lora.left.weight),
                           self.lora.right.weight.T)
         return y

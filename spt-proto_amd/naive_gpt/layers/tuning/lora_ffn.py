@@ -29,6 +29,29 @@ def _plain_router(router) -> bool:
             and router[0].bias is not None)
 
 
+def _block_weights(x: torch.Tensor, weights, why_not):
+    """The layer's frozen block weights as this call reads them.  Stored in halves
+    (utils.tuning.store_frozen_fp16) they go to the fused grouped path as they are -- it runs from their
+    images, to the bits of fp32 storage; a call that path does not take (`why_not()` says why) gets
+    transient fp32 copies (exact), noted as a fallback.  bf16 activations are refused."""
+    if all(w.dtype != torch.float16 for w in weights):
+        return weights
+    from .lora import _f16_refuse, _f16_upcast
+    for w in weights:
+        _f16_refuse(x, w)
+    why = why_not()
+    if why is None:
+        return weights
+    return tuple(_f16_upcast('routed_ffn', w, why) if w.dtype == torch.float16 else w for w in weights)
+
+
+def _grouped_usable(x: torch.Tensor, *frozen_weights) -> bool:
+    """`grouped.usable`, which a frozen contiguous weight stored in halves passes too (what is left in
+    halves by `_block_weights` goes to the fused path)"""
+    return grouped.usable(x, *[None if w is not None and w.dtype == torch.float16 and not w.requires_grad
+                               and w.is_contiguous() else w for w in frozen_weights])
+
+
 def _load_routed(model: nn.Module, source: nn.Module):
     report = model.load_state_dict(source.state_dict(), strict=False)
     if len(report.missing_keys) != 2:      # router weight + bias only: the source
@@ -65,14 +88,20 @@ class LoRARoutedFFN(layers.RoutedFFN):
         return self.router[1](recompute.RecomputedLinear.apply(
             x, origin.input, linear.weight, linear.bias, origin.module))
 
-    def _forward_grouped(self, x: torch.Tensor, origin=None):
+    def _fused(self) -> bool:
+        r = self.fc1.lora.left.weight.size(1)
+        return grouped.activation_code(self.activation) is not None and grouped.fused_usable(r) \
+            and self.fc2.bias is not None and not self.fc2.bias.requires_grad and _plain_router(self.router)
+
+    def _forward_grouped(self, x: torch.Tensor, origin=None, w1=None, w2=None):
         """MI355X path: device-side bucketing + grouped MFMA GEMMs for the frozen base
         weights (layers/sparse/grouped.py); LoRA side paths as dense K = n_blocks * r
         matmuls on the same row space.  No host synchronisation."""
         nb, bs, d, r = self.n_blocks, self.block_size, self.d_model, self.fc1.lora.left.weight.size(1)
+        w1 = self.fc1.weight if w1 is None else w1
+        w2 = self.fc2.weight if w2 is None else w2
         act = grouped.activation_code(self.activation)
-        if act is not None and grouped.fused_usable(r) and self.fc2.bias is not None \
-                and not self.fc2.bias.requires_grad and _plain_router(self.router):
+        if self._fused():
             # four fused block GEMMs, the router and the bucketing of its top-k as ONE autograd
             # node (layers/sparse/grouped.py: RoutedLoRAFFN); coeff = 2 prob (lora_ffn.py:96)
             ext.note_path('routed_ffn', 'fused')
@@ -80,7 +109,7 @@ class LoRARoutedFFN(layers.RoutedFFN):
                 x, self.router[0].weight, self.router[0].bias,
                 self.fc1.lora.left.weight, self.fc1.lora.right.weight,
                 self.fc2.lora.left.weight, self.fc2.lora.right.weight,
-                self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, nb, nb // 2, act,
+                w1, self.fc1.bias, w2, self.fc2.bias, nb, nb // 2, act,
                 origin=origin)
         prob = self._router(x, origin)
         bk = grouped.make_buckets(prob, k=nb // 2, scale=2.0)       # coeff = 2 prob (lora_ffn.py:96)
@@ -91,7 +120,7 @@ class LoRARoutedFFN(layers.RoutedFFN):
         rows = torch.arange(bk.block.numel(), device=x.device)
 
         g1 = grouped.grouped_linear(
-            x, self.fc1.weight, bk.offsets, (bs, d, bs * d, d, 1), gather=bk.token,
+            x, w1, bk.offsets, (bs, d, bs * d, d, 1), gather=bk.token,
             gather_long=bk.token_long, bias=self.fc1.bias.view([nb, bs]), rowscale=coeff)
         # (x L1) R1_g^T as one dense product: the row's r coefficients sit in slice g
         u = torch.matmul(x, self.fc1.lora.left.weight).index_select(0, bk.token_long)
@@ -101,7 +130,7 @@ class LoRARoutedFFN(layers.RoutedFFN):
         h = self.activation(g1 + torch.matmul(u_exp.view(-1, nb * r), r1cat.T))
 
         y2 = grouped.grouped_linear(
-            h, self.fc2.weight, bk.offsets, (d, bs, bs, self.d_feedforward, 1), rowscale=coeff)
+            h, w2, bk.offsets, (d, bs, bs, self.d_feedforward, 1), rowscale=coeff)
         l2cat = self.fc2.lora.left.weight.view([nb, bs, r]).permute(1, 0, 2).reshape(bs, nb * r)
         z = torch.matmul(h, l2cat).view(-1, nb, r)[rows, bk.block]
         ys = y2 + torch.matmul(z, self.fc2.lora.right.weight.T)
@@ -123,9 +152,11 @@ class LoRARoutedFFN(layers.RoutedFFN):
         x_size = x.size()
         origin = recompute.origin_of(x) if x.is_contiguous() else None
         x = x.view([-1, self.d_model])
-        if grouped.usable(x, self.fc1.weight, self.fc1.bias, self.fc2.weight) \
+        fc1_w, fc2_w = _block_weights(x, (self.fc1.weight, self.fc2.weight), lambda: grouped.f16_unusable(
+            x, self.fc1.lora.left.weight.size(1), self._fused(), self.d_model, self.block_size))
+        if _grouped_usable(x, fc1_w, self.fc1.bias, fc2_w) \
                 and self.d_model % 4 == 0 and self.block_size % 4 == 0:
-            return self._forward_grouped(x.contiguous(), origin).view(x_size)
+            return self._forward_grouped(x.contiguous(), origin, fc1_w, fc2_w).view(x_size)
         why_bf16 = self._bf16_unusable(x) if grouped.LORA_BF16 and x.dtype == torch.bfloat16 else 'off'
         if why_bf16 is None:
             # the fused path on bf16 storage (layers/sparse/grouped.py: RoutedLoRAFFNBf16)
@@ -148,10 +179,10 @@ class LoRARoutedFFN(layers.RoutedFFN):
 
         nb, bs = self.n_blocks, self.block_size
         b1 = self.fc1.bias.view([nb, bs])
-        w1 = self.fc1.weight.view([nb, bs, -1])
+        w1 = fc1_w.view([nb, bs, -1])
         r1 = self.fc1.lora.right.weight.view([nb, bs, -1])
         l1 = self.fc1.lora.left.weight
-        w2 = self.fc2.weight.view([-1, nb, bs])
+        w2 = fc2_w.view([-1, nb, bs])
         l2 = self.fc2.lora.left.weight.view([nb, bs, -1])
         r2 = self.fc2.lora.right.weight
 
@@ -190,10 +221,15 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
 
     _router = LoRARoutedFFN._router
 
-    def _forward_grouped(self, x: torch.Tensor, origin=None):
+    def _fused(self) -> bool:
+        return grouped.fused_usable(self.gate.lora.left.weight.size(1)) and _plain_router(self.router)
+
+    def _forward_grouped(self, x: torch.Tensor, origin=None, weights=None):
         """MI355X path, see LoRARoutedFFN._forward_grouped."""
         nb, bs, d, r = self.n_blocks, self.block_size, self.d_model, self.gate.lora.left.weight.size(1)
-        if grouped.fused_usable(r) and _plain_router(self.router):
+        wg, ws, wd = weights if weights is not None else (self.gate.weight, self.side.weight, self.down.weight)
+        base_w = {id(self.gate): wg, id(self.side): ws}
+        if self._fused():
             # three fused block GEMMs forward, router and bucketing inside
             # (layers/sparse/grouped.py: RoutedLoRALLaMAFFN)
             ext.note_path('routed_ffn', 'fused')
@@ -202,7 +238,7 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
                 self.gate.lora.left.weight, self.gate.lora.right.weight,
                 self.side.lora.left.weight, self.side.lora.right.weight,
                 self.down.lora.left.weight, self.down.lora.right.weight,
-                self.gate.weight, self.side.weight, self.down.weight, nb, nb // 2, self.activation,
+                wg, ws, wd, nb, nb // 2, self.activation,
                 origin=origin)
         prob = self._router(x, origin)
         bk = grouped.make_buckets(prob, k=nb // 2, scale=2.0)       # coeff = 2 prob (lora_ffn.py:96)
@@ -212,7 +248,7 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
 
         def up(linear):
             base = grouped.grouped_linear(
-                x, linear.weight, bk.offsets, (bs, d, bs * d, d, 1), gather=bk.token,
+                x, base_w[id(linear)], bk.offsets, (bs, d, bs * d, d, 1), gather=bk.token,
                 gather_long=bk.token_long, rowscale=coeff)
             u = torch.matmul(x, linear.lora.left.weight).index_select(0, bk.token_long)
             u_exp = torch.zeros([u.size(0), nb, r], dtype=u.dtype, device=u.device)
@@ -222,7 +258,7 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
 
         h = self.activation(up(self.gate)) * up(self.side)
         y2 = grouped.grouped_linear(
-            h, self.down.weight, bk.offsets, (d, bs, bs, self.d_feedforward, 1), rowscale=coeff)
+            h, wd, bk.offsets, (d, bs, bs, self.d_feedforward, 1), rowscale=coeff)
         ldcat = self.down.lora.left.weight.view([nb, bs, r]).permute(1, 0, 2).reshape(bs, nb * r)
         z = torch.matmul(h, ldcat).view(-1, nb, r)[rows, bk.block]
         ys = y2 + torch.matmul(z, self.down.lora.right.weight.T)
@@ -241,9 +277,11 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
         x_size = x.size()
         origin = recompute.origin_of(x) if x.is_contiguous() else None
         x = x.view([-1, self.d_model])
-        if grouped.usable(x, self.gate.weight, self.side.weight, self.down.weight) \
-                and self.d_model % 4 == 0 and self.block_size % 4 == 0:
-            return self._forward_grouped(x.contiguous(), origin).view(x_size)
+        weights = _block_weights(x, (self.gate.weight, self.side.weight, self.down.weight),
+                                 lambda: grouped.f16_unusable(x, self.gate.lora.left.weight.size(1), self._fused(),
+                                                              self.d_model, self.block_size))
+        if _grouped_usable(x, *weights) and self.d_model % 4 == 0 and self.block_size % 4 == 0:
+            return self._forward_grouped(x.contiguous(), origin, weights).view(x_size)
         why_bf16 = self._bf16_unusable(x) if grouped.LORA_BF16 and x.dtype == torch.bfloat16 else 'off'
         if why_bf16 is None:
             # the fused path on bf16 storage (layers/sparse/grouped.py: RoutedLoRALLaMAFFNBf16)
@@ -266,13 +304,13 @@ class LoRARoutedLLaMaFFN(layers.RoutedLLaMaFFN):
         route = routing.route_topk(prob, k=self.n_blocks // 2)
 
         nb, bs = self.n_blocks, self.block_size
-        wg = self.gate.weight.view([nb, bs, -1])
+        wg = weights[0].view([nb, bs, -1])
         rg = self.gate.lora.right.weight.view([nb, bs, -1])
         lg = self.gate.lora.left.weight
-        ws = self.side.weight.view([nb, bs, -1])
+        ws = weights[1].view([nb, bs, -1])
         rs = self.side.lora.right.weight.view([nb, bs, -1])
         ls = self.side.lora.left.weight
-        wd = self.down.weight.view([-1, nb, bs])
+        wd = weights[2].view([-1, nb, bs])
         ld = self.down.lora.left.weight.view([nb, bs, -1])
         rd = self.down.lora.right.weight
 

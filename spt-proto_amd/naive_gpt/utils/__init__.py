@@ -2,6 +2,7 @@
 from .adapter import LoRAHandler
 from .adapter import ModuleUpgrader
 from .adapter import SparseLoRAHandler
+from .adapter import store_frozen_fp16
 from .distributed import allreduce_gradients
 from .distributed import broadcast_parameters
 from .distributed import trainable_parameters

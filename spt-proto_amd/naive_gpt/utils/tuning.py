@@ -32,15 +32,22 @@ from . import adapter, checkpoint, distributed
 STAGES = ('lora', 'ffn', 'mha_v1', 'mha_v2')
 
 
+store_frozen_fp16 = adapter.store_frozen_fp16
+
+
 def upgrade_sparse(model: nn.Module, d_lora: int, stages: Iterable[str] = STAGES,
-                   verbose: bool = False) -> nn.Module:
+                   verbose: bool = False, frozen_fp16: bool = False) -> nn.Module:
     """The four-stage upgrade of script/4-sparse-tuning-0.py:33-39 (the handler prints one
-    line per replaced module; silenced unless ``verbose``)."""
+    line per replaced module; silenced unless ``verbose``).  ``frozen_fp16``: afterwards store the
+    frozen base weights in fp16 (`store_frozen_fp16`, strict; the report is left in
+    ``model.frozen_fp16_report``)."""
     sink = contextlib.nullcontext() if verbose else contextlib.redirect_stdout(io.StringIO())
     with sink:
         for stage in stages:
             handler = adapter.SparseLoRAHandler(d_lora=d_lora, stage=stage)
             model = adapter.ModuleUpgrader(handler=handler).visit(model)
+    if frozen_fp16:
+        model.frozen_fp16_report = store_frozen_fp16(model)
     return model
 
 
@@ -49,8 +56,11 @@ class SparseTuner:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, weight_decay: float = 1e-1,
                  gamma: float = 0.9, clip_norm: Optional[float] = 1.0,
-                 aux_weight: float = 1e-2, n_accumulate: int = 1, group=None):
+                 aux_weight: float = 1e-2, n_accumulate: int = 1, group=None, frozen_fp16: bool = False):
         self.model = model
+        # frozen base weights in fp16 (opt-in; exact: `store_frozen_fp16`), before anything below
+        # reads a parameter's storage
+        self.frozen_fp16_report = store_frozen_fp16(model) if frozen_fp16 else None
         self.group = group
         self.world_size = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -103,12 +113,17 @@ class SparseTuner:
         self._updates = 0
 
     @classmethod
-    def from_checkpoint(cls, path: str, d_lora: int = 16, device=None, **kwargs):
+    def from_checkpoint(cls, path: str, d_lora: int = 16, device=None, frozen_fp16: bool = False, **kwargs):
+        """``frozen_fp16``: the frozen base weights are stored in fp16 BEFORE the model moves to
+        `device`, so the fp32 copies never reach it (`store_frozen_fp16`)."""
         model = checkpoint.model_from_checkpoint(path)
         model = upgrade_sparse(model, d_lora=d_lora)
+        report = store_frozen_fp16(model) if frozen_fp16 else None
         if device is not None:
             model = model.to(device)
-        return cls(model, **kwargs)
+        tuner = cls(model, **kwargs)
+        tuner.frozen_fp16_report = report
+        return tuner
 
     # ------------------------------------------------------------------ pieces of a step
     def arm_triggers(self) -> None:

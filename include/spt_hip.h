@@ -750,6 +750,21 @@ int spt_cross_entropy_grad(float *logits, long long ld, long long rows, int n_cl
                            long long ignore_index, void *stream);
 
 /*
+ * The evaluation form of the above (validation: script/4-sparse-tuning-0.py:95-126): logits are
+ * READ ONLY.
+ *   row_loss[i]   = log(sum_j exp(z[i, j])) - z[i, target[i]]          (0 for an ignored row)
+ *   row_argmax[i] = the lowest j in [0, n_classes) with z[i, j] = max_j z[i, j]
+ * Same layout rules, ignored rows, row ownership, expressions and reduction trees as
+ * spt_cross_entropy_grad (row_loss carries its bound); columns n_classes .. ld-1 are never read
+ * into either result, whatever they hold.  A row holding a NaN: NaN loss (when counted), and an
+ * index still inside [0, n_classes) (0 when no element compares above -inf).  Same return codes.
+ * Additive under ABI 40.
+ */
+int spt_cross_entropy_eval(const float *logits, long long ld, long long rows, int n_classes,
+                           const long long *target, long long ignore_index, float *row_loss,
+                           int32_t *row_argmax, void *stream);
+
+/*
  * LayerNorm of the residual stream with the additions around it (the pre-norm wiring of
  * naive_gpt/layers/basic/transformer.py:46-52; nn.LayerNorm arithmetic: biased variance, eps
  * inside the root), or -- rms != 0 -- LLaMA's RMSNorm (utils.py:22-37: no mean, no beta; beta may be

@@ -120,6 +120,8 @@ _PROTOTYPES = {
     'spt_layernorm_backward': ([_c_ptr] * 10 + [ctypes.c_longlong, _c_int, _c_int, _c_ptr], _c_int),
     'spt_cross_entropy_grad': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_ptr,
                                 _c_ptr, ctypes.c_longlong, _c_ptr], _c_int),
+    'spt_cross_entropy_eval': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr,
+                                ctypes.c_longlong, _c_ptr, _c_ptr, _c_ptr], _c_int),
     'spt_lora_down': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int,
                        _c_ptr, ctypes.c_longlong, _c_int] + [_c_ptr] * 2 + [_c_int, _c_ptr], _c_int),
     'spt_lora_down2': ([_c_ptr, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_ptr, _c_int, _c_ptr, _c_int,
@@ -2219,30 +2221,41 @@ def lora_down_grouped(x: torch.Tensor, tables: torch.Tensor, offsets: torch.Tens
 
 
 def cross_entropy_grad_(logits: torch.Tensor, n_classes: int, target: torch.Tensor,
-                        scale: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+                        scale: torch.Tensor, ignore_index: int = -100, evaluate: bool = False):
     """``spt_cross_entropy_grad``: per-row losses [rows] of softmax cross-entropy, and `logits`
     [rows, ld >= n_classes] OVERWRITTEN with (softmax - onehot) * scale (pad columns: zeros).
-    `scale`: a one-element device tensor (1 / number of counted targets for the mean)."""
+    `scale`: a one-element device tensor (1 / number of counted targets for the mean).
+    `evaluate=True` (``spt_cross_entropy_eval``): `logits` is only read, `scale` may be None, and the
+    result is (row_loss fp32 [rows], row_argmax int32 [rows]): the lowest column of each row's
+    maximum over [0, n_classes)."""
     _check_type(logits, torch.float32, 'logits')
     _check_type(target, torch.int64, 'target')
-    _check_type(scale, torch.float32, 'scale')
+    if not (evaluate and scale is None):
+        _check_type(scale, torch.float32, 'scale')
     _require(logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1
              and logits.stride(0) % 4 == 0 and logits.stride(0) >= logits.size(1) >= n_classes
              and logits.data_ptr() % 16 == 0, 'logits: [rows, ld >= n_classes], 16-byte aligned rows')
-    _require(target.is_contiguous() and target.numel() == logits.size(0) and scale.numel() == 1,
+    _require(target.is_contiguous() and target.numel() == logits.size(0)
+             and (scale.numel() == 1 if scale is not None else True),
              'target: one int64 per row; scale: one float')
-    dev = _same_device(logits, target, scale)
+    dev = _same_device(logits, target) if scale is None else _same_device(logits, target, scale)
     rows = logits.size(0)
     lib = load_library()
     with _on(dev):
         loss = torch.empty([rows], dtype=torch.float32, device=dev)
+        top = torch.empty([rows], dtype=torch.int32, device=dev) if evaluate else None
         if rows > 0:
-            rc = lib.spt_cross_entropy_grad(logits.data_ptr(), logits.stride(0), rows, n_classes,
-                                            target.data_ptr(), scale.data_ptr(), loss.data_ptr(),
-                                            ignore_index, _stream(dev))
+            if evaluate:
+                rc = lib.spt_cross_entropy_eval(logits.data_ptr(), logits.stride(0), rows, n_classes,
+                                                target.data_ptr(), ignore_index, loss.data_ptr(),
+                                                top.data_ptr(), _stream(dev))
+            else:
+                rc = lib.spt_cross_entropy_grad(logits.data_ptr(), logits.stride(0), rows, n_classes,
+                                                target.data_ptr(), scale.data_ptr(), loss.data_ptr(),
+                                                ignore_index, _stream(dev))
             if rc != 0:
-                _raise(lib, rc, 'cross_entropy_grad')
-    return loss
+                _raise(lib, rc, 'cross_entropy_eval' if evaluate else 'cross_entropy_grad')
+    return (loss, top) if evaluate else loss
 
 
 def layernorm_form(d: int, rms: bool = False) -> int:

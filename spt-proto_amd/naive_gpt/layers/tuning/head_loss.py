@@ -144,3 +144,69 @@ def lm_head_loss(head, x: torch.Tensor, target: torch.Tensor, ignore_index: int 
     """mean cross-entropy of head(x) against target (nn.CrossEntropyLoss defaults), fused."""
     return _FrozenLoRAHeadLoss.apply(x, head.weight, head.lora.left.weight, head.lora.right.weight,
                                      target, ignore_index)
+
+
+# ---------------------------------------------------------------------------------------------------
+# evaluation: mean loss and the row argmaxes, no gradient, the logits never whole
+
+EVAL_MIN_ROWS = 2048        # rows of a chunk below which the matrix-core GEMM is not taken
+
+
+def eval_usable(head, x: torch.Tensor) -> bool:
+    """`fused_usable` without the condition that the tables are trained: evaluation forms no gradient."""
+    if not (isinstance(head, LoRALinear) and head.bias is None and head._frozen()):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and not x.is_inference()):
+        return False
+    x2 = x.reshape(-1, x.size(-1))
+    rank = head.lora.left.weight.size(1)
+    return _mfma_linear_usable(x2, head.weight, rank) and x2.size(1) % 4 == 0
+
+
+def _chunk_bounds(T: int, max_rows: int):
+    """[0, .., T]: as few chunks as `max_rows` allows, of equal length up to one row, and none under
+    EVAL_MIN_ROWS while T allows it (that bound wins over `max_rows`)."""
+    limit = max(int(max_rows), EVAL_MIN_ROWS)
+    n = max(1, min((T + limit - 1) // limit, T // EVAL_MIN_ROWS))
+    return [i * T // n for i in range(n + 1)]
+
+
+def lm_head_eval(head, x: torch.Tensor, target: torch.Tensor, ignore_index: int = -100, max_rows: int = 8192):
+    """(mean cross-entropy of head(x) against target, argmax of head(x) [T] int32) for a frozen
+    bias-free LoRALinear `head` (`eval_usable`), as validation needs them
+    (script/4-sparse-tuning-0.py:95-126), without the [T, V] logits: the rows go through ONE padded
+    buffer [chunk, Vp] in chunks of at most `max_rows` rows -- written by the grouped GEMM call of
+    `_FrozenLoRAHeadLoss.forward`, read once by ``ext.cross_entropy_grad_(evaluate=True)``, which
+    leaves a loss and the lowest column of the maximum per row.  The mean runs over the counted
+    targets, 0 / 0 = NaN when there is none, as there.  No autograd graph is recorded."""
+    from naive_gpt import ext
+    with torch.no_grad():
+        weight, left, right = head.weight, head.lora.left.weight, head.lora.right.weight
+        V, d = weight.shape
+        x2 = x.detach().reshape(-1, d)
+        T = x2.size(0)
+        Vp = (V + _PAD - 1) // _PAD * _PAD
+        _pad_rows(weight, Vp)
+        images = d % 32 == 0 and x2.is_contiguous()
+        u = _down(x, x2, left, d % 32 == 0).contiguous()               # [T, r]
+        right = right.detach().contiguous()
+        target = target.reshape(-1).contiguous()
+        counted = ((target != ignore_index) & (target >= 0) & (target < V)).sum().to(torch.float32)
+        bounds = _chunk_bounds(T, max_rows)
+        whole = len(bounds) == 2
+        w_image = ext.weight_image(weight) if images else None
+        # (the image of x only when another consumer left one of ALL of x: a chunk has none -- A32)
+        a_image = ext.cached_image(x2, x) if images and whole else None
+        buf = torch.empty([max(hi - lo for lo, hi in zip(bounds, bounds[1:])), Vp], dtype=torch.float32,
+                          device=x2.device)
+        losses, tops = [], []
+        for lo, hi in zip(bounds, bounds[1:]):
+            rows = hi - lo
+            ext.grouped_gemm_fused(x2[lo:hi], weight, _one_group(rows, x2.device), 1, V, d, 0, d, 1, rows,
+                                   a2=u[lo:hi], b2=right, a_image=a_image, w_image=w_image, out=buf[:rows])
+            loss, top = ext.cross_entropy_grad_(buf[:rows], V, target[lo:hi], None, ignore_index, evaluate=True)
+            losses.append(loss)
+            tops.append(top)
+        del buf
+        rows_loss = losses[0] if whole else torch.cat(losses)
+        return rows_loss.sum() / counted, tops[0] if whole else torch.cat(tops)

@@ -9,6 +9,8 @@ from .distributed import trainable_parameters
 from .checkpoint import load_checkpoint
 from .checkpoint import model_from_checkpoint
 from .checkpoint import save_checkpoint
+from .checkpoint import load_tuned
+from .checkpoint import save_tuned
 from .tuning import SparseTuner
 from .tuning import upgrade_sparse
 from .evaluate import evaluate_mmlu

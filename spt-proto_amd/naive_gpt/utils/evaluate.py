@@ -2,7 +2,9 @@
 
 ``load_spt_model``  base checkpoint ({'config', 'state_dict'}, script/1-convert.py:188-195) ->
                     four-stage upgrade -> the tuned adapters' state_dict on top (strict=False; every
-                    key the tuned checkpoint lacks must be a frozen base weight, :44-60)
+                    key the tuned checkpoint lacks must be a frozen base weight, :44-60).  The second
+                    file: a whole upgraded model ({'config', 'state_dict'}), a tuned file of
+                    ``checkpoint.save_tuned``, or the reference's own {'state_dict'} (8-dump-spt.py)
 ``evaluate_mmlu``   the test loop: batches of ``[position, tokens ..]`` (loaders.TruncPadding),
                     logits of ``batch[:, 1:-1]``, perplexity against ``batch[:, 2:]`` and the answer
                     accuracy with the reference's indexing (:64-93) -- ``SparseTuner.validation_step``
@@ -22,7 +24,13 @@ def load_spt_model(ckpt_path: str, spt_ckpt_path: Optional[str] = None, d_lora: 
     model = checkpoint.model_from_checkpoint(ckpt_path)
     model = upgrade_sparse(model, d_lora=d_lora)
     if spt_ckpt_path:
-        _, tuned = checkpoint.load_checkpoint(spt_ckpt_path)
+        raw = torch.load(spt_ckpt_path, map_location='cpu', weights_only=True)
+        if checkpoint.is_tuned(raw):        # save_tuned's file, or the reference's own {'state_dict'}
+            checkpoint.load_tuned_into(model, checkpoint.tuned_state(raw))
+            return model.to(device) if device is not None else model
+        if not isinstance(raw, dict) or 'config' not in raw or 'state_dict' not in raw:
+            raise RuntimeError("not a naive_gpt checkpoint: expected {'config', 'state_dict'}")
+        tuned = raw['state_dict']
         missing = model.load_state_dict(tuned, strict=False).missing_keys
         bad = [name for name in missing if 'lora' in name]
         if bad:

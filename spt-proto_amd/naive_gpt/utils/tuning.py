@@ -125,6 +125,157 @@ class SparseTuner:
         tuner.frozen_fp16_report = report
         return tuner
 
+    # ------------------------------------------------------------------ the state of a run
+    # What Lightning's ModelCheckpoint(save_last=True) keeps for the reference run
+    # (script/4-sparse-tuning-0.py:178-182), minus the frozen base: everything that tuning changes.
+    # Keyed by parameter NAME -- the flat buffer, the fused and the capturable optimiser are forms of
+    # this process, not of the run.
+    STATE_FORMAT = 1
+    EVAL_MAX_ROWS = 8192        # rows per chunk of the fused evaluation head (validation_step)
+
+    @staticmethod
+    def _name_some(names) -> str:
+        names = sorted(names)
+        return ', '.join(names[:4]) + (' ...' if len(names) > 4 else '')
+
+    def _trainable_names(self):
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return [names[id(p)] for p in self.params]
+
+    def _tuned_entries(self):
+        """name -> live tensor for every entry of model.state_dict() that is not a frozen parameter."""
+        return checkpoint.tuned_entries(self.model)
+
+    def _optimizer_entries(self):
+        """[(name, parameter, its optimiser state or None, offset and length in the flat state or None)]."""
+        names = self._trainable_names()
+        if self._flat is not None:
+            state = self.optimizer.state.get(self._flat) or None
+            return [(n, p, state, (o, c)) for n, p, o, c in zip(names, self.params, self._offsets, self._sizes)]
+        return [(n, p, self.optimizer.state.get(p) or None, None) for n, p in zip(names, self.params)]
+
+    def state_dict(self) -> dict:
+        """CPU tensors and plain values: the model's non-frozen entries, both AdamW moments and the
+        step count per trainable name, the hyper-parameters, the scheduler's place and the tuner's
+        own counters.  Partial gradients are not state: raises between the micro-batches of an
+        accumulated step."""
+        if self._micro % self.n_accumulate != 0:
+            raise RuntimeError('SparseTuner.state_dict: {} of {} micro-batches of a step are accumulated; '
+                               'save after the step is applied'.format(self._micro % self.n_accumulate,
+                                                                       self.n_accumulate))
+        exp_avg, exp_avg_sq, steps = {}, {}, {}
+        for name, p, state, where in self._optimizer_entries():
+            if state is None:                   # no step taken yet: what AdamW would start from
+                exp_avg[name], exp_avg_sq[name], steps[name] = torch.zeros(p.shape), torch.zeros(p.shape), 0
+                continue
+            m, v = state['exp_avg'], state['exp_avg_sq']
+            if where is not None:
+                m, v = m[where[0]:where[0] + where[1]].view(p.shape), v[where[0]:where[0] + where[1]].view(p.shape)
+            exp_avg[name], exp_avg_sq[name] = m.detach().cpu().clone(), v.detach().cpu().clone()
+            steps[name] = int(float(state['step']))
+        group = self.optimizer.param_groups[0]
+        return {
+            'format': self.STATE_FORMAT,
+            'model': {k: t.detach().cpu().clone() for k, t in self._tuned_entries().items()},
+            'exp_avg': exp_avg, 'exp_avg_sq': exp_avg_sq, 'step': steps,
+            'lr': float(group['lr']), 'betas': tuple(float(b) for b in group['betas']), 'eps': float(group['eps']),
+            'weight_decay': float(group['weight_decay']),
+            'gamma': float(self.scheduler.gamma), 'last_epoch': int(self.scheduler.last_epoch),
+            'base_lr': float(self.scheduler.base_lrs[0]),
+            '_micro': int(self._micro), 'n_accumulate': int(self.n_accumulate),
+            'clip_norm': None if self.clip_norm is None else float(self.clip_norm),
+            'aux_weight': float(self.aux_weight),
+        }
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copy `state` (of `state_dict()`) into the live tensors, in place: parameters stay the views
+        of the flat buffer they are.  Everything is checked before anything is written."""
+        if self._graph is not None:
+            raise RuntimeError('SparseTuner.load_state_dict: this tuner has captured its step; load the state '
+                               'before capturing (`resume`, then `capture`)')
+        if not isinstance(state, dict) or state.get('format') != self.STATE_FORMAT:
+            raise ValueError('SparseTuner.load_state_dict: not a tuner state of format {}'.format(self.STATE_FORMAT))
+        names = self._trainable_names()
+        for key in ('exp_avg', 'exp_avg_sq', 'step'):
+            missing, unexpected = set(names) - set(state[key]), set(state[key]) - set(names)
+            if missing:
+                raise ValueError('tuner state: {} lacks trainable parameters: {}'.format(key, self._name_some(missing)))
+            if unexpected:
+                raise ValueError('tuner state: {} names parameters this tuner does not train: {}'.format(
+                    key, self._name_some(unexpected)))
+        live = self._tuned_entries()
+        missing, unexpected = set(live) - set(state['model']), set(state['model']) - set(live)
+        if missing:
+            raise ValueError('tuner state: model entries missing: {}'.format(self._name_some(missing)))
+        if unexpected:
+            raise ValueError('tuner state: unexpected model entries: {}'.format(self._name_some(unexpected)))
+        shapes = [k for k, t in live.items() if tuple(t.shape) != tuple(state['model'][k].shape)]
+        by_name = dict(zip(names, self.params))
+        shapes += [key + ':' + n for key in ('exp_avg', 'exp_avg_sq') for n in names
+                   if tuple(state[key][n].shape) != tuple(by_name[n].shape)]
+        if shapes:
+            raise ValueError('tuner state: shapes differ: {}'.format(self._name_some(shapes)))
+        if int(state['n_accumulate']) != self.n_accumulate:
+            raise ValueError('tuner state: saved with n_accumulate {}, this tuner has {}'.format(
+                state['n_accumulate'], self.n_accumulate))
+        if int(state['_micro']) % self.n_accumulate != 0:
+            raise ValueError('tuner state: taken between the micro-batches of an accumulated step')
+        if self._flat is not None:
+            self._check_flat_views()
+            if len({int(state['step'][n]) for n in names}) > 1:
+                self._unflatten()           # parameters with step counts of their own: one entry each
+        with torch.no_grad():
+            for key, t in live.items():
+                t.copy_(state['model'][key])
+            group = self.optimizer.param_groups[0]
+            on_device = bool(group.get('capturable') or group.get('fused'))
+            for owner in self._optimised():
+                if not self.optimizer.state.get(owner):         # as AdamW initialises it on its first step
+                    self.optimizer.state[owner] = {
+                        'step': torch.zeros((), dtype=torch.float32, device=owner.device) if on_device
+                        else torch.tensor(0.0, dtype=torch.float32),
+                        'exp_avg': torch.zeros_like(owner, memory_format=torch.preserve_format),
+                        'exp_avg_sq': torch.zeros_like(owner, memory_format=torch.preserve_format)}
+            for name, p, entry, where in self._optimizer_entries():
+                m, v = entry['exp_avg'], entry['exp_avg_sq']
+                if where is not None:
+                    m, v = m[where[0]:where[0] + where[1]].view(p.shape), v[where[0]:where[0] + where[1]].view(p.shape)
+                m.copy_(state['exp_avg'][name])
+                v.copy_(state['exp_avg_sq'][name])
+                if torch.is_tensor(entry['step']):
+                    entry['step'].fill_(float(state['step'][name]))
+                else:
+                    entry['step'] = float(state['step'][name])
+            groups = [group]
+            if self.scheduler.optimizer is not self.optimizer:      # (the capturable tuner's stand-in)
+                groups.append(self.scheduler.optimizer.param_groups[0])
+            for g in groups:
+                if torch.is_tensor(g['lr']):
+                    g['lr'].fill_(float(state['lr']))
+                else:
+                    g['lr'] = float(state['lr'])
+                g['initial_lr'] = float(state['base_lr'])
+            group['betas'] = tuple(state['betas'])
+            group['eps'], group['weight_decay'] = float(state['eps']), float(state['weight_decay'])
+        self.scheduler.gamma = float(state['gamma'])
+        self.scheduler.last_epoch = int(state['last_epoch'])
+        self.scheduler.base_lrs = [float(state['base_lr'])]
+        self.scheduler._last_lr = [float(state['lr'])]
+        self._micro = int(state['_micro'])
+        self.clip_norm = state['clip_norm']
+        self.aux_weight = float(state['aux_weight'])
+
+    def save(self, path: str) -> None:
+        torch.save(self.state_dict(), f=path)
+
+    @classmethod
+    def resume(cls, base_ckpt: str, state_path: str, device=None, **kwargs):
+        """`from_checkpoint(base_ckpt, device=device, **kwargs)` with the state `save` wrote on top.
+        The state holds no frozen weight, so `frozen_fp16=True` applies to the base alone."""
+        tuner = cls.from_checkpoint(base_ckpt, device=device, **kwargs)
+        tuner.load_state_dict(torch.load(state_path, map_location='cpu', weights_only=True))
+        return tuner
+
     # ------------------------------------------------------------------ pieces of a step
     def arm_triggers(self) -> None:
         armed = set()
@@ -451,19 +602,52 @@ class SparseTuner:
         self._graph_keepalive = ext.held_by_caches()
         self._graph_launches = -1
 
+    def _eval_head(self, src: torch.Tensor, target: torch.Tensor):
+        """(loss, argmax [B, S]) of the fused evaluation head (layers/tuning/head_loss.py:
+        `lm_head_eval`), (loss, logits) of the library head behind the same `model.hidden`, or None:
+        CPU batches, models with hooks and other loss functions keep `shared_step` untouched."""
+        from naive_gpt.layers.tuning import head_loss
+        model, fn = self.model, self.loss_fn
+        plain = (type(fn) is nn.CrossEntropyLoss and fn.weight is None and fn.reduction == 'mean'
+                 and fn.label_smoothing == 0.0)
+        hooked = bool(model._forward_hooks or model._forward_pre_hooks
+                      or getattr(getattr(model, 'lm_output', None), '_forward_hooks', None))
+        if not (src.is_cuda and plain and not hooked and hasattr(model, 'hidden') and hasattr(model, 'lm_output')):
+            return None
+        from naive_gpt import ext
+        h = model.hidden(src)
+        if head_loss.eval_usable(model.lm_output, h):
+            ext.note_path('head_eval', 'fused')
+            loss, top = head_loss.lm_head_eval(model.lm_output, h, target, fn.ignore_index,
+                                                max_rows=self.EVAL_MAX_ROWS)
+            return loss, top.view(src.shape)
+        ext.note_path('head_eval', 'library', fallback=True,
+                      why=lambda: 'head {} on h {}: the fused evaluation takes a frozen bias-free LoRALinear, '
+                          'fp32, >= 2048 tokens'.format(type(model.lm_output).__name__, tuple(h.shape)))
+        output = model.lm_output(h)
+        return fn(output.flatten(end_dim=-2), target=target.flatten()), output
+
     @torch.no_grad()
     def validation_step(self, batch: torch.Tensor) -> dict:
         """Perplexity and the MMLU answer accuracy of script/4-sparse-tuning-0.py:95-126.
         The accuracy keeps the reference's indexing: ``batch[:, position]`` with a vector
         ``position`` selects a [B, B] grid (every row against every row's answer
-        position), and the mean runs over that grid."""
+        position), and the mean runs over that grid.  On the GPU the loss and the predictions come
+        from the fused evaluation head where it applies (`_eval_head`): the grid is then gathered
+        from the row argmaxes, and no [tokens, vocabulary] tensor is formed."""
         assert batch.dim() == 2
         self.model.eval()
         target = batch[:, 2:]
-        output, loss = self.shared_step(batch[:, 1:-1], target=target)
         position = batch[:, 0]
         answers = batch[:, position]
-        predict = torch.argmax(output[:, position - 2, :], dim=-1)
+        head = self._eval_head(batch[:, 1:-1], target)
+        if head is None:
+            head = self.shared_step(batch[:, 1:-1], target=target)[::-1]
+        loss, output = head
+        if output.dim() == 2:               # the row argmaxes [B, S]
+            predict = output[:, position - 2].long()
+        else:
+            predict = torch.argmax(output[:, position - 2, :], dim=-1)
         accuracy = torch.eq(predict, answers).float().mean()
         return {'loss': loss, 'ppl': torch.exp(loss), 'accuracy': accuracy}
 

@@ -5,7 +5,9 @@
 
 ``--data_root`` holds ``mmlu/{dev,test,val,auxiliary_train}/*.csv``; ``--tokenizer`` is a directory a
 ``transformers`` tokenizer was saved to, or ``bytes`` (a byte-level stand-in: it runs the pipeline,
-its numbers mean nothing for a model trained on another vocabulary).  Prints one JSON line."""
+its numbers mean nothing for a model trained on another vocabulary).  ``--spt_ckpt`` is a tuned file of
+either form (``utils.save_tuned``'s, or the reference's own ``{'state_dict'}``) or a whole upgraded model.
+Prints one JSON line."""
 import argparse
 import json
 import os
@@ -20,7 +22,8 @@ from naive_gpt import loaders, utils  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--ckpt', default='.data/opt-125m.ckpt', help='base model checkpoint {config, state_dict}')
-    ap.add_argument('--spt_ckpt', default=None, help='tuned adapters (state_dict over the upgraded model)')
+    ap.add_argument('--spt_ckpt', default=None, help='tuned file: checkpoint.save_tuned\'s, the reference\'s own {state_dict} (8-dump-spt.py), '
+                                                    'or a whole upgraded model {config, state_dict}')
     ap.add_argument('--data_root', default=os.path.join(os.path.expanduser('~'), 'Public/Datasets/text'))
     ap.add_argument('--tokenizer', default='bytes')
     ap.add_argument('--seq_length', type=int, default=512)

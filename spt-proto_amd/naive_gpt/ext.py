@@ -284,9 +284,9 @@ def capture_tag(dev=None) -> int:
     """0 when torch's current stream on `dev` (a torch.device; default: the current device) is not
     being captured into a HIP graph, else a number that names THAT capture
     (hipStreamGetCaptureInfo's id + 1, asked of the HIP runtime this library links).  It is the
-    stream `_stream(dev)` hands the kernels.  Every host-side memo below tags its entries with it
-    and serves an entry only under the tag it was made with.  Outside -> inside: a hit would leave
-    the launch that made the by-product out of the graph, and a replay on new contents of the same
+    stream `_stream(dev)` hands the kernels.  Every host-side memo is a `_Stamped` (below): it tags
+    its entries with it and serves one only under the tag it was made with.  Outside -> inside: a hit would
+    leave the launch that made the by-product out of the graph, and a replay on new contents of the same
     buffers would read the old by-product at its old address (the version counter moves, but
     nothing in a graph looks at it).  Inside -> outside, or into another capture: the entry's
     memory belongs to that graph's pool and is rewritten by every replay.  Eager callers on the
@@ -310,15 +310,88 @@ def capture_tag(dev=None) -> int:
     return ident.value + 1 if status.value != 0 else 0
 
 
+MEMOS = {}          # name -> _Stamped: every memo of the package (`clear_memos`, the tests' helpers)
+
+
+class _Stamped:
+    """{owner -> (stamp, value)}: a host-side by-product kept between calls.
+
+    An entry belongs to the OWNER object: keyed by `id` and held through a weak reference whose
+    callback removes it, so no lifetime is extended and an address handed to another tensor cannot
+    alias (a tensor's elementwise `==` rules out weakref.WeakKeyDictionary).  The `stamp` is the
+    caller's, compared with `==`: `_version`, which every in-place write moves, and whatever else the
+    value depends on.  An entry is served only under the `capture_tag` it was made with (of the stream
+    on `at.device`), asked only where owner and stamp already match, and once when an entry is made:
+    `find` hands its answer to the `keep` that follows.  `bound()`: how many entries stay, the least
+    recently used leaving first (default: all, for the life of their owners).  `name`: registers the
+    memo in `MEMOS`.
+
+    `frozen_from_eager`, the one exception: a capture is also served the EAGER entry (tag 0) of an owner
+    that does not require a gradient.  Nothing in a captured step writes a frozen weight, and what the
+    warm-up computed need not be computed again by every replay (`held_by_caches` keeps it alive for
+    the graph).  A TRAINED weight's eager entry is not served to a capture: the in-graph optimiser moves
+    the weight between two replays, and the by-product has to be made inside the graph."""
+    __slots__ = ('data', 'bound', 'frozen_from_eager')
+
+    def __init__(self, name=None, bound=None, frozen_from_eager=False):
+        self.data = {} if bound is None else collections.OrderedDict()
+        self.bound, self.frozen_from_eager = bound, frozen_from_eager
+        if name is not None:
+            MEMOS[name] = self
+
+    def find(self, owner, stamp, at):         # -> (value | None, the tag on at.device if it was asked | None)
+        hit = self.data.get(id(owner))
+        if hit is None or hit[0]() is not owner or hit[1] != stamp:
+            return None, None
+        tag = capture_tag(at.device)
+        if hit[2] == tag or (self.frozen_from_eager and hit[2] == 0 and not owner.requires_grad):
+            if self.bound is not None:
+                self.data.move_to_end(id(owner))
+            return hit[3], tag
+        return None, tag
+
+    def keep(self, owner, stamp, value, at, tag=None):
+        key, data = id(owner), self.data
+        data[key] = (weakref.ref(owner, lambda _, k=key: data.pop(k, None)), stamp,
+                     capture_tag(at.device) if tag is None else tag, value)
+        if self.bound is not None:
+            data.move_to_end(key)
+            while len(data) > self.bound():
+                data.popitem(last=False)
+
+    def values(self) -> list:
+        return [entry[3] for entry in self.data.values()]
+
+    def clear(self):
+        self.data.clear()
+
+
+class _PerParameter(_Stamped):
+    """By-products of a weight, stamped (data_ptr, _version), with the exception for frozen ones."""
+    __slots__ = ()
+
+    def __init__(self, name=None):
+        super().__init__(name, frozen_from_eager=True)
+
+    def get(self, w):
+        return self.find(w, (w.data_ptr(), w._version), w)[0]
+
+    def put(self, w, value):
+        self.keep(w, (w.data_ptr(), w._version), value, w)
+
+
+def clear_memos():
+    """Empty every registered memo (`drop_images`: those of `ext` that hold images and norms)."""
+    for memo in MEMOS.values():
+        memo.clear()
+
+
 def held_by_caches() -> list:
     """Every device tensor the module-level caches of this package hold for later calls: frozen
     weights' row norms and (SPT_WEIGHT_IMAGES=keep) images.  A captured HIP graph that read one of
     them reads its ADDRESS at every replay, whatever becomes of the cache entry (`drop_images()`,
     a parameter re-homed): `SparseTuner.capture` keeps this list alive for the life of its graph."""
-    held = []
-    for cache in (_WEIGHT_IMAGES, _WEIGHT_NORMS):
-        held += [entry[2] for entry in cache.data.values()]
-    return held
+    return _WEIGHT_IMAGES.values() + _WEIGHT_NORMS.values()
 
 
 class _NoGuard:
@@ -911,21 +984,20 @@ def csr_transpose(indptr: torch.Tensor, indices: torch.Tensor, d_head: int = 64)
     return buf
 
 
+_TRANSPOSED = _Stamped('transposed')
+
+
 def transposed_for(indptr: torch.Tensor, indices: torch.Tensor, d_head: int = 64) -> torch.Tensor:
-    """``csr_transpose`` memoised on the ``indices`` tensor object itself (keyed by the
-    tensors' in-place version counters and the head size), so the A^T products of one
-    backward pass -- grad_K in sddmm's backward, grad_V in spmm's -- share one build.  The
-    cache dies with the tensor.  A build made outside a graph capture is not served inside one,
-    nor the other way round (`capture_tag`)."""
-    key = (indices._version, indptr.data_ptr(), indptr._version, int(d_head))
-    cached = getattr(indices, '_spt_transposed', None)
-    tag = None
-    if cached is not None and cached[0] == key:         # (the tag is asked only where all else matches)
-        tag = capture_tag(indices.device)
-        if cached[2] == tag:
-            return cached[1]
-    buf = csr_transpose(indptr, indices, d_head)
-    indices._spt_transposed = (key, buf, capture_tag(indices.device) if tag is None else tag)
+    """``csr_transpose`` memoised on the ``indices`` tensor object (stamped with the tensors'
+    in-place version counters and the head size), so the A^T products of one backward pass --
+    grad_K in sddmm's backward, grad_V in spmm's -- share one build.  The entry dies with the
+    tensor.  A build made outside a graph capture is not served inside one, nor the other way
+    round (`_Stamped`)."""
+    stamp = (indices._version, indptr.data_ptr(), indptr._version, int(d_head))
+    buf, tag = _TRANSPOSED.find(indices, stamp, indices)
+    if buf is None:
+        buf = csr_transpose(indptr, indices, d_head)
+        _TRANSPOSED.keep(indices, stamp, buf, indices, tag)
     return buf
 
 
@@ -1288,15 +1360,12 @@ def split_bf16(x: torch.Tensor) -> SplitImage:
 
 
 # Images of the activations most recently split.  The q / k / v projections of a block read ONE
-# tensor: the first splits it, the other two find the image here.  An entry is identified by
-# the OWNER object (the tensor the layer was called with, held through a weak reference -- no
-# lifetime is extended, and an address handed to another tensor cannot alias) and its
-# `_version` (every in-place write moves it), its shape and the capture it was made in
-# (`capture_tag`: q / k / v share one image inside a capture too, but a capture never reads an
-# image that eager code made, nor eager code one of a graph's).  Two entries: they are as large as
-# activations.
-_IMAGE_CACHE = collections.OrderedDict()
+# tensor: the first splits it, the other two find the image here.  The owner is the tensor the
+# layer was called with, the stamp its `_version` and the shape of the matrix (`_Stamped`: q / k / v
+# share one image inside a capture too, but a capture never reads an image that eager code made,
+# nor eager code one of a graph's).  Two entries: they are as large as activations.
 IMAGE_CACHE_ENTRIES = 2
+_IMAGE_CACHE = _Stamped('images', bound=lambda: IMAGE_CACHE_ENTRIES)
 
 
 def image_of(x: torch.Tensor, owner: torch.Tensor = None) -> SplitImage:
@@ -1305,20 +1374,11 @@ def image_of(x: torch.Tensor, owner: torch.Tensor = None) -> SplitImage:
     owner = x if owner is None else owner
     if owner.is_inference():
         return split_bf16(x)
-    key = id(owner)
-    hit = _IMAGE_CACHE.get(key)
-    stamp, tag = (owner._version, tuple(x.shape)), None
-    if hit is not None and hit[0]() is owner and hit[1][:2] == stamp:    # (the tag: only where all else matches)
-        tag = capture_tag(x.device)
-        if hit[1][2] == tag:
-            _IMAGE_CACHE.move_to_end(key)
-            return hit[2]
-    img = split_bf16(x)
-    _IMAGE_CACHE[key] = (weakref.ref(owner, lambda _, k=key: _IMAGE_CACHE.pop(k, None)),
-                         stamp + (capture_tag(x.device) if tag is None else tag,), img)
-    _IMAGE_CACHE.move_to_end(key)
-    while len(_IMAGE_CACHE) > IMAGE_CACHE_ENTRIES:
-        _IMAGE_CACHE.popitem(last=False)
+    stamp = (owner._version, tuple(x.shape))
+    img, tag = _IMAGE_CACHE.find(owner, stamp, x)
+    if img is None:
+        img = split_bf16(x)
+        _IMAGE_CACHE.keep(owner, stamp, img, x, tag)
     return img
 
 
@@ -1327,24 +1387,14 @@ def cached_image(x: torch.Tensor, owner: torch.Tensor = None):
     owner = x if owner is None else owner
     if owner.is_inference():
         return None
-    hit = _IMAGE_CACHE.get(id(owner))
-    if hit is not None and hit[0]() is owner and hit[1][:2] == (owner._version, tuple(x.shape)) \
-            and hit[1][2] == capture_tag(x.device):
-        return hit[2]
-    return None
+    return _IMAGE_CACHE.find(owner, (owner._version, tuple(x.shape)), x)[0]
 
 
 def put_image(x: torch.Tensor, owner: torch.Tensor, img: SplitImage) -> None:
     """Hand the cache an image made elsewhere (``lora_down(..., want_image=True)``)."""
     owner = x if owner is None else owner
-    if owner.is_inference():
-        return
-    key = id(owner)
-    _IMAGE_CACHE[key] = (weakref.ref(owner, lambda _, k=key: _IMAGE_CACHE.pop(k, None)),
-                         (owner._version, tuple(x.shape), capture_tag(x.device)), img)
-    _IMAGE_CACHE.move_to_end(key)
-    while len(_IMAGE_CACHE) > IMAGE_CACHE_ENTRIES:
-        _IMAGE_CACHE.popitem(last=False)
+    if not owner.is_inference():
+        _IMAGE_CACHE.keep(owner, (owner._version, tuple(x.shape)), img, x)
 
 
 def drop_images():
@@ -1358,38 +1408,7 @@ def drop_images():
 # (SPT_WEIGHT_IMAGES unset or 'step'): a weight is re-split every time it is used (4 MiB ->
 # ~4 us, ~1.5 % of a step) and nothing is kept; SPT_WEIGHT_IMAGES=keep holds the image for the
 # life of the parameter (dropped when `_version` moves).
-class _PerParameter:
-    """{parameter -> value} keyed by identity (a tensor's `==` is elementwise, which rules out
-    weakref.WeakKeyDictionary); an entry dies with its parameter or when `_version` moves.
-
-    Entries carry the `capture_tag` they were made under.  Eager code is served eager entries only.
-    A graph capture is served its own entries and, for a parameter that does not require a
-    gradient, eager ones: nothing in a captured step writes a frozen weight, and what the warm-up
-    computed need not be computed again by every replay (`held_by_caches` keeps it alive for the
-    graph).  A TRAINED weight's eager entry is not served to a capture: the in-graph optimiser
-    moves the weight between two replays, and the by-product has to be made inside the graph."""
-
-    def __init__(self):
-        self.data = {}
-
-    def get(self, w):
-        hit = self.data.get(id(w))
-        if hit is not None and hit[0]() is w and hit[1] == (w.data_ptr(), w._version):
-            tag = capture_tag(w.device)
-            if hit[3] == tag or (hit[3] == 0 and not w.requires_grad):
-                return hit[2]
-        return None
-
-    def put(self, w, value):
-        key = id(w)
-        self.data[key] = (weakref.ref(w, lambda _, k=key: self.data.pop(k, None)),
-                          (w.data_ptr(), w._version), value, capture_tag(w.device))
-
-    def clear(self):
-        self.data.clear()
-
-
-_WEIGHT_IMAGES = _PerParameter()
+_WEIGHT_IMAGES, _WEIGHT_NORMS = _PerParameter('weight_images'), _PerParameter('weight_norms')
 KEEP_WEIGHT_IMAGES = os.environ.get('SPT_WEIGHT_IMAGES', 'step') == 'keep'
 
 
@@ -1397,9 +1416,6 @@ def row_norms(x: torch.Tensor) -> torch.Tensor:
     """Euclidean norm of every row of a matrix (fp32 [rows]).  Of a fp16-stored weight: of its fp32
     upcast (transient), by the same call -- the same norms, so the same near-the-kink cells."""
     return torch.linalg.vector_norm(x.detach().float(), dim=1)
-
-
-_WEIGHT_NORMS = _PerParameter()
 
 
 def weight_row_norms(w: torch.Tensor) -> torch.Tensor:

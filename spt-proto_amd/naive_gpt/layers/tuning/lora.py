@@ -11,6 +11,7 @@ import weakref
 import torch
 from torch import nn
 
+from naive_gpt import ext
 from . import recompute
 
 
@@ -53,7 +54,6 @@ def tall_tn(a: torch.Tensor, b: torch.Tensor, chunk: int = 256) -> torch.Tensor:
         # one call of libspt_hip (lora_side.hip: spt_tall_tn) -- the same HBM-bound pass as the
         # library's batched product + sum, at a quarter of their host time (the step makes ~260
         # of these products and is within 10 % of being host-bound)
-        from naive_gpt import ext
         if a.size(1) >= b.size(1) and ext.tall_tn_supported(a, b):
             ext.note_path('tall_tn', 'kernel')
             return ext.tall_tn(a, b)[0]
@@ -79,7 +79,6 @@ def tall_tn_many(pairs):
     live = [i for i, p in enumerate(pairs) if p is not None]
     out = [None] * len(pairs)
     if len(live) >= 2 and pairs[live[0]][0].is_cuda and pairs[live[0]][0].size(0) >= 512:
-        from naive_gpt import ext
         wides, narrows = [pairs[i][0] for i in live], [pairs[i][1] for i in live]
         if len(live) <= 4 and ext.tall_tn_batchable(wides, narrows):
             ext.note_path('tall_tn', 'kernel_batch')
@@ -115,7 +114,6 @@ def _f16(weight: torch.Tensor) -> bool:
 def _f16_upcast(site: str, weight: torch.Tensor, why) -> torch.Tensor:
     """The fp32 copy of ONE fp16-stored weight for ONE call that cannot run from its image (exact;
     released with the call) -- noted as a fallback, never silent."""
-    from naive_gpt import ext
     ext.note_path(site, 'f16_upcast', fallback=True,
                   why=lambda: 'fp16-stored frozen weight {} upcast for this call: {}'.format(
                       tuple(weight.shape), why() if callable(why) else why))
@@ -152,7 +150,6 @@ def _mfma_gemm(a, weight, n, k, ldn, ldk, bias=None, a2=None, b2=None, images=Fa
     GEMM time).  The weight's image is kept with the frozen parameter; the activation's costs
     one pass over it (about what the GEMM saves), so it pays where several GEMMs read the same
     input -- the q / k / v projections -- which the small image cache of `ext` detects."""
-    from naive_gpt import ext
     rows = a.size(0)
     a_image = w_image = None
     if (images or _f16(weight)) and k % 32 == 0 and a.is_contiguous():
@@ -169,12 +166,12 @@ def _mfma_gemm(a, weight, n, k, ldn, ldk, bias=None, a2=None, b2=None, images=Fa
 # The q / k / v projections read the same tensor: their three tables go side by side through ONE
 # pass over it (ext.lora_down: u for each adapter, plus the split image the three GEMMs read).
 # `prepare_shared` is called by the attention module in front of the three linear layers; each
-# layer then finds its u here.  One entry, alive as long as the input tensor is.
-_SHARED = {}
+# layer then finds its u here.  One entry, alive as long as the input tensor is: {id(left): u},
+# owned by the input and stamped with its `_version`.
+_SHARED = ext._Stamped('lora.shared')
 
 
 def prepare_shared(x: torch.Tensor, linears) -> None:
-    from naive_gpt import ext
     _SHARED.clear()
     if not (x.is_cuda and x.dim() >= 2 and not x.is_inference()):
         return
@@ -192,25 +189,18 @@ def prepare_shared(x: torch.Tensor, linears) -> None:
             return
         u, image, _ = ext.lora_down(x2, table, want_image=True, block_major=True)
     ext.put_image(x2, x, image)
-    _SHARED[id(x)] = (weakref.ref(x, lambda _, k=id(x): _SHARED.pop(k, None)), (x._version, ext.capture_tag(x.device)),
-                      {id(l): u[i] for i, l in enumerate(lefts)}, ext.capture_tag)
+    _SHARED.keep(x, (x._version,), {id(l): u[i] for i, l in enumerate(lefts)}, x)
 
 
 def _shared_u(x: torch.Tensor, left: torch.Tensor):
-    hit = _SHARED.get(id(x))
-    if hit is None or hit[0]() is not x or hit[1][0] != x._version:
-        return None
-    # (products made outside a graph capture are not served inside one, nor the other way round:
-    # ext.capture_tag, which the entry carries -- no import on this path)
-    if hit[1][1] != hit[3](x.device):
-        return None
-    return hit[2].get(id(left))
+    # (products made outside a graph capture are not served inside one, nor the other way round)
+    found = None if x.is_inference() else _SHARED.find(x, (x._version,), x)[0]
+    return None if found is None else found.get(id(left))
 
 
 def _down(x: torch.Tensor, x2: torch.Tensor, left: torch.Tensor, images: bool):
     """u = x2 @ left: found (prepare_shared), or one pass that also leaves x2's split image when
     the GEMM behind it wants one and none is cached, or the library product."""
-    from naive_gpt import ext
     u = _shared_u(x, left)
     if u is not None:
         return u
@@ -227,7 +217,6 @@ def _down_grad(dy2: torch.Tensor, right: torch.Tensor, out: torch.Tensor = None)
     """dU = dY R [T, r] of a LoRA layer's backward: the same tall-times-narrow pass as the forward's
     x L (spt_lora_down; a library GEMM costs the host four times as much per call), optionally
     into a column slice `out` of a wider matrix."""
-    from naive_gpt import ext
     if ext.lora_down_supported(dy2, right):
         ext.note_path('lora_down', 'kernel')
         return ext.lora_down(dy2, right, out=out)
@@ -248,7 +237,6 @@ class _FrozenLoRALinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, left, right):
-        from naive_gpt import ext
         x2 = x.reshape(-1, x.size(-1))
         n, k = weight.shape
         _f16_refuse(x, weight)
@@ -283,7 +271,6 @@ class _FrozenLoRALinear(torch.autograd.Function):
         grad_x = None
         if ctx.needs_input_grad[0]:
             n, k = weight.shape
-            from naive_gpt import ext
             mfma = ctx.mfma and dy2.is_contiguous() and _mfma_linear_usable(dy2, weight, left.size(1), False)
 
             def why():
@@ -375,7 +362,6 @@ class _FrozenLoRAQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        from naive_gpt import ext
         weights, biases = params[0:3], params[3:6]
         lefts, rights = params[6:9], params[9:12]
         v_apart = bool(params[12])
@@ -433,7 +419,6 @@ class _FrozenLoRAQKV(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dys):
-        from naive_gpt import ext
         saved = ctx.saved_tensors
         x2, u3 = saved[0], saved[1]
         weights, lefts, rights = saved[2:5], saved[5:8], saved[8:11]
@@ -518,7 +503,6 @@ class _FrozenLoRAQKV(torch.autograd.Function):
 
 
 def qkv_usable(x: torch.Tensor, linears) -> bool:
-    from naive_gpt import ext
     if not (x.is_cuda and x.dim() >= 2 and x.dtype == torch.float32 and not x.is_inference()):
         return False
     if not all(isinstance(m, LoRALinear) and m._frozen() for m in linears):
@@ -604,7 +588,6 @@ class _LookupRows(torch.autograd.Function):
         ids, = ctx.saved_tensors
         g = grad.reshape(ids.numel(), -1)
         if g.dtype == torch.float32 and g.size(1) % 4 == 0 and g.stride(1) == 1 and g.stride(0) % 4 == 0:
-            from naive_gpt import ext
             return None, ext.embedding_rows_backward(g, ids.reshape(-1), ctx.rows)
         # (other widths / dtypes: torch's scatter-add; deterministic only without duplicates)
         out = torch.zeros([ctx.rows, g.size(1)], dtype=g.dtype, device=g.device)

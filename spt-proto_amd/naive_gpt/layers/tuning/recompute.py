@@ -81,7 +81,7 @@ def lazy(origin):
                 rms)
 
 
-_last = [None, None]          # (key, tensor): the norm output most recently recomputed
+_last = [None, None]   # (key, tensor) of the last recompute; no capture tag: `tag` drops it at every forward
 
 
 def output(module: nn.Module, input: torch.Tensor) -> torch.Tensor:

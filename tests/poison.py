@@ -120,15 +120,14 @@ def same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
 
 
 def fresh_caches(*indices):
-    """Empty every cache that could carry a result from one run into the next: the split images,
-    weight images and weight norms of ext, the csr_transpose memo on each given `indices` tensor,
-    the adapters' shared down products, and the attention layers' indptr cache."""
+    """Empty every cache that could carry a result from one run into the next: every registered memo
+    of the package (`ext.clear_memos`: split images, weight images and norms, the csr_transpose memo,
+    the adapters' shared down products, and whatever registers later), the norm output last
+    recomputed, and the attention layers' indptr cache.  (`indices`: what callers hand on as `*memo`;
+    the transposed memo no longer needs them to be found.)"""
     from naive_gpt import ext
     from naive_gpt.layers.sparse.attention import _SparseCore
-    from naive_gpt.layers.tuning import lora
-    ext.drop_images()
-    lora._SHARED.clear()
-    for t in indices:
-        if hasattr(t, '_spt_transposed'):
-            del t._spt_transposed
+    from naive_gpt.layers.tuning import recompute
+    ext.clear_memos()
+    recompute.release()
     _SparseCore._indptr_cache.clear()

@@ -212,14 +212,12 @@ def _on_side_stream(call):
     return outs
 
 
-def _memo_entries(memo):
+def _memo_entries():
     """What the identity-keyed memos hold right now.  Should a capture have taken an address out of
     one of them, a replay reads that address: it must stay allocated until the case ends, so that a
     stale read is a wrong value for the comparison to find and never a memory error."""
     from naive_gpt import ext
-    from naive_gpt.layers.tuning import lora
-    return (list(ext._IMAGE_CACHE.values()), list(lora._SHARED.values()),
-            [getattr(t, '_spt_transposed', None) for t in memo])
+    return [memo.values() for memo in ext.MEMOS.values()]
 
 
 def captured(call, memo=(), before=None):
@@ -236,7 +234,7 @@ def captured(call, memo=(), before=None):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         outs = call()
-    return graph, _flatten(outs), (warm, outs, ext.held_by_caches(), _memo_entries(memo))
+    return graph, _flatten(outs), (warm, outs, ext.held_by_caches(), _memo_entries())
 
 
 Runs = collections.namedtuple('Runs', 'outs0 outs0_again got1 want1 want1_again got2 mode')

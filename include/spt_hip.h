@@ -232,6 +232,8 @@ int spt_spmm_transposed(const int32_t *indptr, const void *transposed, const flo
  * softmax_forward_cuda(indptr, indices, values) -> output
  *   reference: extension/entry.cpp:33-36, extension/softmax.cu:84-114 (kernel :7-47)
  * y = mask * exp(v) / max(1e-9, sum_row mask * exp(v)), mask = indices <= row.
+ * indices and every [B, nnz] float operand of the three softmax entries 16-byte aligned (SPT_ESHAPE):
+ * rows whose bounds are multiples of 4 (and nnz % 4 == 0) move four entries per lane.
  */
 int spt_softmax_forward(const int32_t *indptr, const int32_t *indices,
                         const float *values, float *output, int batch_size,
@@ -408,7 +410,8 @@ int spt_attention_mfma_backward_bf16(const void *tiles, int layout, const uint16
  *     W_g(n, k) = w[g * w_group_stride + n * w_ldn + k * w_ldk]   (w_ldk == 1 or w_ldn == 1)
  * a [*, lda] (lda >= k), out [n_rows, n]; gather / bias [n_groups, n] / rowscale may be
  * NULL.  offsets is DEVICE memory (bucket sizes never visit the host).  Requires
- * k % 4 == 0, lda % 4 == 0 and 16-byte aligned weight rows.
+ * k % 4 == 0, lda % 4 == 0 and 16-byte aligned weight rows: w 16-byte aligned, and w_ldn
+ * (w_ldk when w_ldn == 1) and w_group_stride multiples of 4 (SPT_ESHAPE).
  */
 int spt_grouped_gemm(const float *a, const int32_t *gather, const float *w,
                      const float *bias, const float *rowscale,
@@ -492,7 +495,7 @@ typedef struct SptGroupedGemm {
      * 8 bytes per element (256 segments; n_rows * n / 64 elements are 25 x the expected
      * number).  With it the GEMM only queues them and a second launch recomputes all of them in
      * parallel; without it, or where a segment overflows, the epilogue recomputes them itself,
-     * one after another (~2 us each).  16-byte aligned; contents on return are unspecified. */
+     * one after another (~2 us each).  16-byte aligned (SPT_ESHAPE); contents on return are unspecified. */
     void *relu_queue;
     int64_t relu_queue_bytes;
     int64_t ldo;               /* row stride (floats) of out, out2, h_in, s_in; 0: n.  A padded
@@ -672,7 +675,8 @@ int spt_split_f16(const void *src_f16, void *image, long long rows, int cols, lo
  *                  optional by-products of the same read: `image` (spt_split_bf16's layout,
  *                  spt_split_bf16_bytes(rows, k) bytes) and `norms` [rows] (row 2-norms) -- NULL
  *                  to skip.  k % 32 == 0, n in {16, 32, 48, 64}: SPT_EUNSUP otherwise (callers
- *                  then use a library GEMM).
+ *                  then use a library GEMM).  x (four floats per lane) and image 16-byte aligned,
+ *                  ldx % 4 == 0 (SPT_ESHAPE) -- in every entry of this family; l, u, norms 4-byte.
  * exact == 0: split-bf16 matrix-core products as in spt_grouped_gemm, <= 2^-15 relative per
  * product.  exact != 0: u in exact fp32 (the fp32-input MFMA, an fp32 FMA chain per element):
  * for the u that feeds the GEMM in front of a ReLU (lora_ffn.py:99-101), where a 2^-16 error
@@ -689,13 +693,13 @@ int spt_lora_down_grouped_cols(const float *x, long long ldx, long long rows, in
                                long long l_group_stride, int n, const int32_t *offsets, int n_groups,
                                float *u, long long ldu, void *stream);
 /* spt_lora_down for n_tables (<= 4) SEPARATE tables [k, 16] lying table_stride floats apart (table t at
- * l + t * table_stride): u as n_tables block-major matrices [rows, 16], exactly what one table
+ * l + t * table_stride, table_stride % 4 == 0: SPT_ESHAPE): u as n_tables block-major matrices [rows, 16], exactly what one table
  * [k, 16 n_tables] of the concatenated columns gives -- without making that copy every step. */
 int spt_lora_down_tables(const float *x, long long ldx, long long rows, int k, const float *l,
                          int n_tables, long long table_stride, float *u, void *image, float *norms,
                          int exact, void *stream);
 /* spt_lora_down with a SECOND table: u gets one more block of 16 columns = x . l2^T for a row-major
- * l2 [n2 <= 16, k] (an nn.Linear weight as stored; 16-byte aligned); columns n2 .. 15 of that block are 0.
+ * l2 [n2 <= 16, k] (an nn.Linear weight as stored; 16-byte aligned: SPT_ESHAPE); columns n2 .. 15 of that block are 0.
  * Exact form only (exact != 0; SPT_EUNSUP otherwise).  `n` counts the columns of `l` only (n + 16 <= 64); u_block_major as above: (n / 16 + 1) matrices
  * [rows, 16].  The routed FFN's router logits ride the pass that forms x . L1 (feedforward.py:22-25). */
 int spt_lora_down2(const float *x, long long ldx, long long rows, int k, const float *l, int n,
@@ -769,7 +773,10 @@ int spt_cross_entropy_eval(const float *logits, long long ld, long long rows, in
  * naive_gpt/layers/basic/transformer.py:46-52; nn.LayerNorm arithmetic: biased variance, eps
  * inside the root), or -- rms != 0 -- LLaMA's RMSNorm (utils.py:22-37: no mean, no beta; beta may be
  * NULL, mean is written as 0, dbeta as 0).  rows x d fp32, contiguous; the widths are those for which
- * spt_layernorm_form(d, rms) != 0 (SPT_EUNSUP else).
+ * spt_layernorm_form(d, rms) != 0 (SPT_EUNSUP else).  Every [rows, d] and [d] operand is read or written
+ * four floats per lane: x, r, gamma, beta, s, y of the forward and s, dy, gamma, dskip, dx, partial of the
+ * backward 16-byte aligned (SPT_ESHAPE; a slice of a flat parameter buffer at 16-byte granularity
+ * qualifies); mean, rstd, dgamma / dbeta 4-byte.
  *   forward   s = x + r (r, s may be NULL: s = x, nothing written);  y = LN(s) gamma + beta;
  *             mean, rstd [rows] for the backward.
  *   backward  dx = dLN(dy) (+ dskip, may be NULL: the gradient arriving over the skip path);
@@ -857,7 +864,8 @@ int spt_tall_tn_bf16(const void *wide, long long ldw, const float *narrow, long 
  *   pos[t * k + j]       the row of token t's j-th selected block (ascending block id)
  * prob [n_tokens, n_blocks] fp32; token / block [n_tokens * k], offsets [n_blocks + 1],
  * pos [n_tokens * k] int32.  Ties go to the lower block index.  One workgroup:
- * n_blocks <= 8 and n_tokens <= 65536 (SPT_EUNSUP otherwise).
+ * n_blocks <= 8 and n_tokens <= 65536 (SPT_EUNSUP otherwise).  prob 16-byte aligned (SPT_ESHAPE; also
+ * in spt_route_topk_coeff): four blocks are one load.
  */
 int spt_route_topk(const float *prob, int32_t *token, int32_t *block, int32_t *offsets,
                    int32_t *pos, int n_tokens, int n_blocks, int k, void *stream);
@@ -905,7 +913,7 @@ int spt_route_logit_backward(const float *dcoeff, const int32_t *pos, const int3
  *   out[p] = (sum_j dot_main[p, j] + sum_j dot_act[p, j] - <du[p], u[token[p]]> - <dzt[token[p]], z[p]>)
  *            / max(coeff[p], floor_value)
  * dot_main, dot_act [n_rows, width]: SptGroupedGemm.pdot_main / pdot_act of the EPI_DACT GEMM;
- * du, z [n_rows, rank]; u, dzt [tokens, rank]; rank % 4 == 0.
+ * du, z [n_rows, rank]; u, dzt [tokens, rank]; rank % 4 == 0 and these four 16-byte aligned (SPT_ESHAPE).
  */
 int spt_ffn_coeff_grad(const float *dot_main, const float *dot_act, int width, const float *du,
                        const float *u, const float *dzt, const float *z, const int32_t *token,
@@ -945,7 +953,8 @@ int spt_rotary(const float *const *x, int n_parts, int n_rot, float *out, long l
  * backward, ONE pass over [rows, n] (n % 4 == 0) instead of ~10 elementwise / reduction launches:
  *   grad_gate = grad_h * side * silu'(gate),  grad_side = grad_h * silu(gate),
  *   dots [3, rows] = <grad_h, h>, <grad_gate, gate>, <grad_side, side> per row
- * (the three inner products of the router-coefficient gradient).  All pointers 16-byte aligned.
+ * (the three inner products of the router-coefficient gradient).  gate, side, h and the four gradients
+ * 16-byte aligned (SPT_ESHAPE); dots (one float per store: rows need not be a multiple of 4) 4-byte.
  */
 int spt_swiglu_forward(const float *gate, const float *side, float *h, long long n_elements, void *stream);
 int spt_swiglu_backward(const float *grad_h, const float *gate, const float *side, float *grad_gate,
@@ -967,7 +976,8 @@ int spt_swiglu_backward_dots_bf16(const void *grad_h, const void *gate, const vo
  * the SORTED id list with sorted_ids[t] == id, added in ascending t in fp64 (deterministic; a
  * non-finite gradient row stays in its own id's row).  sorted_ids / order: int64, device memory, the
  * stable sort of the flattened ids and its permutation; grad [n_ids, width] fp32 (row stride ldg),
- * width % 4 == 0; workspace: spt_embedding_rows_backward_workspace_bytes(n_ids, width) bytes.  Launch
+ * width % 4 == 0, ldg % 4 == 0, ldo % 4 == 0 (the row stride of out), grad and out 16-byte and workspace
+ * 8-byte aligned (SPT_ESHAPE); workspace: spt_embedding_rows_backward_workspace_bytes(n_ids, width) bytes.  Launch
  * shapes depend on n_ids alone (replayable as part of a captured HIP graph); ids outside [0, n_rows)
  * are ignored.
  */
@@ -979,7 +989,8 @@ int spt_embedding_rows_backward(const float *grad, long long ldg, const long lon
 /*
  * Un-bucketing: out[t, :] = bias + sum_{j < k} rows[pos[t * k + j], :] (bias may be NULL).
  * Replaces the reference's per-block `y[mask] += ...` scatter (lora_ffn.py:107-111) with a
- * gather in a fixed order: deterministic, no atomics.  d % 4 == 0.
+ * gather in a fixed order: deterministic, no atomics.  d % 4 == 0; rows, bias and out 16-byte aligned
+ * (SPT_ESHAPE; also in spt_rows_combine_side).
  */
 int spt_rows_combine(const float *rows, const int32_t *pos, const float *bias, float *out,
                      int n_tokens, int k, int d, void *stream);

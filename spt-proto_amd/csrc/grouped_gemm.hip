@@ -240,6 +240,9 @@ static int launch_grouped(GroupedArgs g, int epilogue, void *stream) {
     if (g.ldo < g.N) return SPT_EINVAL;
     if (g.accumulate && epilogue != EPI_PLAIN) return SPT_EUNSUP;
     if (g.K % 4 != 0 || g.lda % 4 != 0) return SPT_ESHAPE;       // float4 rows of A
+    // 16-byte aligned weight rows (halves: 8, four per load); the queue's counters and int2 entries
+    if ((reinterpret_cast<uintptr_t>(g.w) & (g.w_f16 ? 7 : 15)) != 0) return SPT_ESHAPE;
+    if ((reinterpret_cast<uintptr_t>(g.fix_count) & 15) != 0) return SPT_ESHAPE;
     if (g.ldk != 1 && g.ldn != 1) return SPT_EUNSUP;
     if (g.ldk == 1 && (g.ldn % 4 != 0 || g.gstride % 4 != 0)) return SPT_ESHAPE;
     if (g.ldk != 1 && (g.ldk % 4 != 0 || g.N % 4 != 0 || g.gstride % 4 != 0)) return SPT_ESHAPE;
@@ -417,11 +420,17 @@ extern "C" int spt_split_f16(const void *src_f16, void *image, long long rows, i
     return SPT_OK;
 }
 
+// float4 per lane from rows, bias (NULL: none) and to out
+static bool rc_misaligned(const void *rows, const void *bias, const void *out) {
+    return ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(bias) |
+             reinterpret_cast<uintptr_t>(out)) & 15) != 0;
+}
+
 extern "C" int spt_rows_combine(const float *rows, const int32_t *pos, const float *bias,
                                 float *out, int n_tokens, int k, int d, void *stream) {
     if (!rows || !pos || !out) return SPT_EINVAL;
     if (n_tokens <= 0 || k <= 0 || d <= 0) return SPT_EINVAL;
-    if (d % 4 != 0) return SPT_ESHAPE;
+    if (d % 4 != 0 || rc_misaligned(rows, bias, out)) return SPT_ESHAPE;
     hipLaunchKernelGGL(rows_combine_kernel, dim3((unsigned)n_tokens), dim3(256), 0,
                        (hipStream_t)stream, rows, pos, bias, out, n_tokens, k, d / 4, nullptr, nullptr, 0);
     SPT_LAUNCH_CHECK();
@@ -433,7 +442,8 @@ extern "C" int spt_rows_combine_side(const float *rows, const int32_t *pos, cons
                                      int n_tokens, int k, int d, void *stream) {
     if (!rows || !pos || !out || !side || !side_w) return SPT_EINVAL;
     if (n_tokens <= 0 || k <= 0 || d <= 0 || n_side <= 0 || n_side > 64) return SPT_EINVAL;
-    if (d % 4 != 0 || (reinterpret_cast<uintptr_t>(side_w) & 15) != 0) return SPT_ESHAPE;
+    if (d % 4 != 0 || (reinterpret_cast<uintptr_t>(side_w) & 15) != 0 || rc_misaligned(rows, bias, out))
+        return SPT_ESHAPE;
     hipLaunchKernelGGL(rows_combine_kernel, dim3((unsigned)n_tokens), dim3(256), 0,
                        (hipStream_t)stream, rows, pos, bias, out, n_tokens, k, d / 4, side, side_w, n_side);
     SPT_LAUNCH_CHECK();

@@ -22,6 +22,8 @@
 // rsqrt(var + eps)); row sums are butterfly trees, so results differ from the library's in the
 // last bits only.  That holds up to d = 2048 (d / 256 = 1, 2, 3, 4, 8; RMS also 16); wider rows are
 // shared by several waves (the wide-row kernels below).  spt_layernorm_form() is the width gate.
+#include <initializer_list>
+
 #include "spt_common.h"
 #include "norm_apply.h"
 
@@ -458,6 +460,13 @@ extern "C" int spt_layernorm_form(int d, int rms) {
     }
 }
 
+// float4 per lane: any of these pointers off a 16-byte boundary (NULL counts as aligned)
+static bool ln_misaligned(std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15) != 0;
+}
+
 extern "C" int spt_add_layernorm_forward(const float *x, const float *r, const float *gamma,
                                          const float *beta, float *s, float *y, float *mean,
                                          float *rstd, long long rows, int d, float eps, int rms,
@@ -466,6 +475,7 @@ extern "C" int spt_add_layernorm_forward(const float *x, const float *r, const f
     if (rows <= 0 || d <= 0) return SPT_EINVAL;
     const int form = spt_layernorm_form(d, rms);
     if (!form) return SPT_EUNSUP;
+    if (ln_misaligned({x, r, gamma, beta, s, y})) return SPT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(ln_blocks(rows)), block(LN_THREADS);
     // KERNEL<..., ADD, RMS>: `...` is NV (a wave per row) or NV, W (wide rows)
@@ -513,6 +523,7 @@ extern "C" int spt_layernorm_backward(const float *s, const float *dy, const flo
     const int form = spt_layernorm_form(d, rms);
     if (!form) return SPT_EUNSUP;
     if (dbeta != dgamma + d) return SPT_EINVAL;        // one [2, d] buffer: reduced in one launch
+    if (ln_misaligned({s, dy, gamma, dskip, dx, partial})) return SPT_ESHAPE;
     hipStream_t st = (hipStream_t)stream;
     const int nblk = ln_blocks(rows);
     const dim3 grid(nblk), block(LN_THREADS);

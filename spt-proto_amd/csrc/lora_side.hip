@@ -250,14 +250,15 @@ static int lora_down_any(const float *x, long long ldx, long long rows, int k, c
                          int r_k = 0, int32_t *counts = nullptr) {
     if (!x || !l || !u) return SPT_EINVAL;
     if (rows <= 0 || k <= 0 || n <= 0 || ldx < k) return SPT_EINVAL;
-    if (l2 && (n2 <= 0 || n2 > 16 || offsets || (reinterpret_cast<uintptr_t>(l2) & 15) != 0)) return SPT_EINVAL;
+    if (l2 && (n2 <= 0 || n2 > 16 || offsets)) return SPT_EINVAL;
     // (with a second table `n` counts its block of 16 too; the first table is [k, n - 16])
     // (table_stride != 0: n / 16 separate tables [k, 16], table_stride floats apart)
-    if (table_stride != 0 && (l2 || offsets || table_stride % 4 != 0)) return SPT_EINVAL;
+    if (table_stride != 0 && (l2 || offsets)) return SPT_EINVAL;
     const int n_l = table_stride ? 16 : (l2 ? n - 16 : n);
     const long long l_bstride = table_stride ? table_stride : 16;
     if (k % 32 != 0 || n % 16 != 0 || n > 64 || n_l <= 0) return SPT_EUNSUP;
     if (ldx % 4 != 0 || !ls_aligned(x) || (image && !ls_aligned(image))) return SPT_ESHAPE;
+    if ((l2 && !ls_aligned(l2)) || table_stride % 4 != 0) return SPT_ESHAPE;
     if (offsets && (n_groups <= 0 || n_groups > 64)) return SPT_EINVAL;
     const long long nblk = (rows + 15) / 16 + (offsets ? n_groups : 0);
     if (nblk > 0x7FFFFFFFll) return SPT_EUNSUP;

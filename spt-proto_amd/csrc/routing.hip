@@ -440,6 +440,9 @@ extern "C" int spt_embedding_rows_backward(const float *grad, long long ldg, con
     using namespace spt;
     if (!grad || !sorted_ids || !order || !out || !workspace) return SPT_EINVAL;
     if (n_ids <= 0 || n_rows <= 0 || width <= 0 || width % 4 || ldg % 4 || ldo % 4) return SPT_ESHAPE;
+    if (((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(out)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+        return SPT_ESHAPE;                            // float4 rows of grad and out, doubles in workspace
     if (n_rows * ldo > 0x7fffffffLL || n_ids * (width / 4) > 0x7fffffffLL * 256) return SPT_EUNSUP;
     hipStream_t s = (hipStream_t)stream;
     SPT_ZERO_WORDS(out, n_rows * ldo, s);            // rows no id names: zero gradient
@@ -642,7 +645,9 @@ extern "C" int spt_ffn_coeff_grad(const float *dot_main, const float *dot_act, i
                                   float *out, int n_rows, int rank, void *stream) {
     if (!dot_main || !dot_act || !du || !u || !dzt || !z || !token || !coeff || !out) return SPT_EINVAL;
     if (n_rows <= 0 || width <= 0 || rank <= 0) return SPT_EINVAL;
-    if (rank % 4 != 0) return SPT_ESHAPE;
+    if (rank % 4 != 0 || ((reinterpret_cast<uintptr_t>(du) | reinterpret_cast<uintptr_t>(u) |
+                           reinterpret_cast<uintptr_t>(dzt) | reinterpret_cast<uintptr_t>(z)) & 15) != 0)
+        return SPT_ESHAPE;                            // float4 along the rank
     hipLaunchKernelGGL(ffn_coeff_grad_kernel, dim3((n_rows + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, dot_main, dot_act, width, du, u, dzt, z, token, coeff,
                        floor_value, out, n_rows, rank);

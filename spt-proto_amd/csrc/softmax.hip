@@ -10,6 +10,8 @@
 // Semantics kept from the reference: mask_p = indices[p] <= row, no max subtraction,
 // denominator max(1e-9, sum) (softmax.cu:30), and in the backward the *clamped*
 // c = max(1e-9, sum mask*y*dy) (softmax.cu:69).
+#include <initializer_list>
+
 #include "spt_common.h"
 
 namespace spt {
@@ -149,11 +151,19 @@ static int softmax_launch(const int32_t *indptr, const int32_t *indices, const f
 
 using namespace spt;
 
+// the rows whose bounds allow it move four entries per lane: every [B, nnz] operand 16-byte aligned
+static bool sm_misaligned(std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15) != 0;
+}
+
 extern "C" int spt_softmax_forward(const int32_t *indptr, const int32_t *indices,
                                    const float *values, float *output, int batch_size,
                                    int seq_length, int nnz, void *stream) {
     if (!indptr || !indices || !values || !output) return SPT_EINVAL;
     if (batch_size <= 0 || seq_length <= 0 || nnz < 0) return SPT_EINVAL;
+    if (sm_misaligned({indices, values, output})) return SPT_ESHAPE;
     if (nnz == 0) return SPT_OK;
     return softmax_launch<0>(indptr, indices, values, nullptr, output, batch_size, seq_length,
                              nnz, (hipStream_t)stream);
@@ -165,6 +175,7 @@ extern "C" int spt_softmax_backward(const int32_t *indptr, const int32_t *indice
                                     int nnz, void *stream) {
     if (!indptr || !indices || !output || !grad_output || !grad_values) return SPT_EINVAL;
     if (batch_size <= 0 || seq_length <= 0 || nnz < 0) return SPT_EINVAL;
+    if (sm_misaligned({indices, output, grad_output, grad_values})) return SPT_ESHAPE;
     if (nnz == 0) return SPT_OK;
     return softmax_launch<1>(indptr, indices, output, grad_output, grad_values, batch_size,
                              seq_length, nnz, (hipStream_t)stream);
@@ -178,6 +189,7 @@ extern "C" int spt_softmax_backward_clamped(const int32_t *indptr, const int32_t
     if (!indptr || !indices || !output || !grad_output || !clamped_scores || !grad_scores)
         return SPT_EINVAL;
     if (batch_size <= 0 || seq_length <= 0 || nnz < 0 || !(clampv > 0.0f)) return SPT_EINVAL;
+    if (sm_misaligned({indices, output, grad_output, clamped_scores, grad_scores})) return SPT_ESHAPE;
     if (nnz == 0) return SPT_OK;
     return softmax_launch<2>(indptr, indices, output, grad_output, grad_scores, batch_size,
                              seq_length, nnz, (hipStream_t)stream, clamped_scores, scale, clampv);

@@ -1985,8 +1985,9 @@ def swiglu_backward(dh: torch.Tensor, g: torch.Tensor, s: torch.Tensor):
 
 def embedding_rows_backward(grad: torch.Tensor, ids: torch.Tensor, n_rows: int) -> torch.Tensor:
     """Gradient of ``table[ids]`` with respect to the table (``spt_embedding_rows_backward``):
-    grad ``[T, width]`` fp32, ids ``[T]`` int64 -> ``[n_rows, width]``; deterministic, shape-static."""
-    _check_dim(grad, 2, 'grad')
+    grad ``[T, width]`` fp32 (unit column stride, any row stride % 4: a column slice), ids ``[T]`` int64 ->
+    ``[n_rows, width]``; deterministic, shape-static."""
+    _require(isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dim() == 2, 'grad must be a CUDA tensor of dim 2')
     _check_type(grad, torch.float32, 'grad')
     _check_type(ids, torch.int64, 'ids')
     T, width = grad.shape
@@ -2297,7 +2298,10 @@ def layernorm_takes(is_cuda: bool, dtype, shape, d: int, rms: bool = False) -> b
 
 
 def layernorm_supported(x: torch.Tensor, d: int, rms: bool = False) -> bool:
-    return layernorm_takes(x.is_cuda, x.dtype, x.shape, d, rms)
+    """`layernorm_takes`, and x 16-byte aligned (the kernels move four floats per lane).  This is the gate a
+    layer asks before it picks the kernels; the other operands' alignment (as every alignment the header
+    states) the C entry checks itself, and its SPT_ESHAPE is raised as a RuntimeError."""
+    return layernorm_takes(x.is_cuda, x.dtype, x.shape, d, rms) and x.data_ptr() % 16 == 0
 
 
 def add_layernorm_forward(x: torch.Tensor, r, gamma: torch.Tensor, beta, eps: float, rms: bool = False):
@@ -2306,7 +2310,8 @@ def add_layernorm_forward(x: torch.Tensor, r, gamma: torch.Tensor, beta, eps: fl
     d = x.size(-1)
     _require(layernorm_supported(x, d, rms) and x.is_contiguous() and gamma.is_contiguous()
              and gamma.numel() == d and gamma.dtype == torch.float32,
-             'add_layernorm: contiguous CUDA fp32 [..., d], d a width that layernorm_form(d, rms) takes')
+             'add_layernorm: contiguous CUDA fp32 [..., d], 16-byte aligned, d a width that layernorm_form(d, rms) '
+             'takes')
     if not rms:
         _require(beta is not None and beta.is_contiguous() and beta.numel() == d, 'beta: [d]')
     if r is not None:
@@ -2335,7 +2340,8 @@ def layernorm_backward(s: torch.Tensor, dy: torch.Tensor, gamma: torch.Tensor, m
     dbeta is zeros)."""
     d = s.size(-1)
     _require(layernorm_supported(s, d, rms) and s.is_contiguous() and dy.is_contiguous()
-             and dy.shape == s.shape and dy.dtype == torch.float32, 'layernorm_backward: s, dy [..., d]')
+             and dy.shape == s.shape and dy.dtype == torch.float32,
+             'layernorm_backward: s, dy [..., d], 16-byte aligned')
     if dskip is not None:
         _require(dskip.shape == s.shape and dskip.is_contiguous() and dskip.dtype == torch.float32,
                  'dskip: like s')

@@ -73,24 +73,31 @@ def _kind(norm: nn.Module):
     return None
 
 
-def usable(norm: nn.Module, x: torch.Tensor) -> bool:
+def usable(norm: nn.Module, x: torch.Tensor, r=None) -> bool:
+    """The kernels take this norm of x (+ r): a width they have, and x, r, gamma and beta 16-byte aligned
+    (the contract of spt_add_layernorm_forward; a tuner's flat parameter slices are)."""
     kind = _kind(norm)
     if kind is None:
         return False
     from naive_gpt import ext
-    return ext.layernorm_supported(x, kind[0].numel(), kind[3]) and not x.is_inference()
+    gamma, beta = kind[0], kind[1]
+    return ext.layernorm_supported(x, gamma.numel(), kind[3]) and not x.is_inference() \
+        and (gamma.data_ptr() | (0 if beta is None else beta.data_ptr()) | (0 if r is None else r.data_ptr())) & 15 == 0
 
 
 def add_norm(norm: nn.Module, x: torch.Tensor, r):
     """(x + r, norm(x + r)); r None: (x, norm(x))."""
     from naive_gpt import ext
-    if usable(norm, x):
+    if usable(norm, x, r):
         ext.note_path('norm', 'kernel')
         gamma, beta, eps, rms = _kind(norm)
         if r is None:
             return x, _LayerNorm.apply(x, gamma, beta, eps, rms)
         return _AddLayerNorm.apply(x, r, gamma, beta, eps, rms)
     ext.note_path('norm', 'library', fallback=x.is_cuda and not x.is_inference(),
-                  why=lambda: '{} on x {} {}'.format(type(norm).__name__, tuple(x.shape), x.dtype))
+                  why=lambda: '{} on x {} {}{}'.format(
+                      type(norm).__name__, tuple(x.shape), x.dtype,
+                      '' if all(t is None or t.data_ptr() % 16 == 0 for t in (x, r) + tuple(norm.parameters()))
+                      else ', an operand off a 16-byte boundary'))
     s = x if r is None else x + r
     return s, norm(s)

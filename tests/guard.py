@@ -7,8 +7,10 @@ allocation of its own,
 
     [lead band: band_bytes][the tensor's bytes][trail band: band_bytes]
 
-whose first tensor byte is 512-byte aligned, as the caching allocator would give it, and whose trail
-band begins at the tensor's last byte plus one, with no rounding gap.  One allocation per tensor,
+whose first tensor byte is 512-byte aligned, as the caching allocator would give it (or, with
+`skew`, lies that many bytes past a 512-byte boundary: the weakest placement the library's contract
+still accepts, tests/test_gpu_placement.py), and whose trail band begins at the tensor's last byte
+plus one, with no rounding gap.  One allocation per tensor,
 never an arena: `ext.back_to_back` and `ext.spacing_of` compare `untyped_storage().data_ptr()`, and
 `ext._bounds_behind` reads the storage size behind `row_sum` (of the forward's own `stats` buffer,
 which always has the bounds; a foreign `row_sum` would find the trail band there).  `home(t, state)`
@@ -60,10 +62,11 @@ class Guard:
     `unguarded` results of the patched functions that could not be rebuilt, by allocating function
     in `sites`.  Holds every allocation until `release()`."""
 
-    def __init__(self, pattern, band_bytes, devices, originals):
+    def __init__(self, pattern, band_bytes, devices, originals, skew=0):
         assert pattern in PATTERNS, pattern
         assert band_bytes > 0 and band_bytes % ALIGN == 0, 'band_bytes: a positive multiple of 512'
-        self.pattern, self.band_bytes, self.devices = pattern, band_bytes, tuple(devices)
+        assert isinstance(skew, int) and 0 <= skew < ALIGN and skew % 16 == 0, 'skew: a multiple of 16 below 512'
+        self.pattern, self.band_bytes, self.devices, self.skew = pattern, band_bytes, tuple(devices), skew
         self.empty, self.empty_like, self.new_empty = originals
         self.allocations = self.homes = self.unguarded = 0
         self.sites = {}
@@ -101,8 +104,9 @@ class Guard:
         nbytes, band = span * item, self.band_bytes
         if min(strides, default=0) < 0 or ALIGN % item:
             raise ValueError('cannot carve strides {} of {}'.format(strides, dtype))
-        buf = self.empty([band + nbytes + band + ALIGN], dtype=torch.uint8, device=device)
+        buf = self.empty([band + nbytes + band + 2 * ALIGN], dtype=torch.uint8, device=device)
         lead = (-buf.data_ptr()) % ALIGN + band          # the CPU allocator aligns to 64 only
+        lead += self.skew
         block_view = buf[lead:lead + nbytes].view(dtype)
         t = block_view.as_strided(tuple(shape), tuple(strides), lead // item)
         block = _Block(buf, lead, nbytes, band, t, caller)
@@ -110,7 +114,7 @@ class Guard:
             view.copy_(self._band_pattern(dtype, buf.device, first))
         self.blocks.append(block)
         self.sites[caller] = self.sites.get(caller, 0) + 1
-        assert numel == 0 or t.data_ptr() == buf.data_ptr() + lead and t.data_ptr() % ALIGN == 0
+        assert numel == 0 or t.data_ptr() == buf.data_ptr() + lead and t.data_ptr() % ALIGN == self.skew
         return t
 
     def rebuild(self, t, caller):
@@ -155,13 +159,14 @@ class Guard:
 
 
 @contextlib.contextmanager
-def guarded(pattern: str, band_bytes: int = 1 << 20, devices=('cuda',)):
+def guarded(pattern: str, band_bytes: int = 1 << 20, devices=('cuda',), skew: int = 0):
     """Inside the block, what `torch.empty`, `torch.empty_like` and `torch.Tensor.new_empty` create
     on `devices` lies between two bands of `band_bytes` each (a multiple of 512) that hold `pattern`.
+    Their first byte lies `skew` bytes (a multiple of 16 below 512) past a 512-byte boundary.
     Yields the `Guard`; call its `verify()` after a device synchronize.  The default band is for
     single entries; a whole training step keeps every allocation alive and takes a smaller one."""
     empty, empty_like, new_empty = torch.empty, torch.empty_like, torch.Tensor.new_empty
-    state = Guard(pattern, band_bytes, devices, (empty, empty_like, new_empty))
+    state = Guard(pattern, band_bytes, devices, (empty, empty_like, new_empty), skew)
 
     def caller():
         return sys._getframe(2).f_code.co_name
@@ -184,8 +189,8 @@ def guarded(pattern: str, band_bytes: int = 1 << 20, devices=('cuda',)):
 
 def home(t: torch.Tensor, state: Guard, caller: str = None, device='cuda'):
     """A copy of `t` (on the CPU, or on the device already) inside a guarded allocation on `device`
-    whose bands hold the state's pattern: same values, dtype, shape and, as `.cuda()` keeps them,
-    strides."""
+    whose bands hold the state's pattern, at the state's skew: same values, dtype, shape and, as
+    `.cuda()` keeps them, strides."""
     caller = caller or sys._getframe(1).f_code.co_name
     with torch.no_grad():
         strides = state.empty_like(t, device='meta').stride()

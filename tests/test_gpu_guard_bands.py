@@ -55,11 +55,12 @@ def _plain_run(case):
     return outs
 
 
-def _guarded_run(case, pattern, what):
-    """build() and call() with every operand and every allocation between bands of `pattern`
+def _guarded_run(case, pattern, what, skew=0):
+    """build() and call() with every operand and every allocation between bands of `pattern`, its
+    first byte `skew` bytes past a 512-byte boundary (test_gpu_placement: 16)
     -> (outputs, the build's check, the guard's state), the bands verified."""
     fresh_caches()
-    with guard.guarded(pattern) as state:
+    with guard.guarded(pattern, skew=skew) as state:
         def to_home(t):
             return guard.home(t, state, caller=sys._getframe(1).f_code.co_name)
         plain_dev, suite._dev = suite._dev, to_home
@@ -103,13 +104,12 @@ def test_entry_stays_inside_its_buffers(entry, case):
             check(outs)
 
 
-@pytest.mark.parametrize('kind', ['opt', 'llama'])
-def test_model_step_stays_inside_its_buffers(kind):
+def _guarded_steps(kind, skew=0):
     """One SparseTuner step of the upgraded model of test_model_step_ignores_what_its_buffers_held,
     on the same paths, with every allocation of the step between 64 KiB bands (the state keeps them
     all alive until verify(); parameters and the batch stay where they are).  Loss and gradients
     within that test's 1e-5 of the unguarded step, not in the same bits: the attention backward's
-    atomics are the same exception as there."""
+    atomics are the same exception as there.  `skew`: of every allocation of the guarded steps."""
     from naive_gpt import ext
     run, tuner = suite.model_step(kind)
 
@@ -121,7 +121,7 @@ def test_model_step_stays_inside_its_buffers(kind):
             torch.cuda.synchronize()
             state = None
         else:
-            with guard.guarded(pattern, band_bytes=65536) as state:
+            with guard.guarded(pattern, band_bytes=65536, skew=skew) as state:
                 outs = run()
                 torch.cuda.synchronize()
         outs = [o.detach().clone() for o in outs]
@@ -148,3 +148,9 @@ def test_model_step_stays_inside_its_buffers(kind):
                     _close(b, a, 'step output {} under {}'.format(i, pattern), rtol=1e-5)
     finally:
         tuner.release()
+
+
+@pytest.mark.parametrize('kind', ['opt', 'llama'])
+def test_model_step_stays_inside_its_buffers(kind):
+    """`_guarded_steps` with every allocation where the allocator would put it (skew 0)."""
+    _guarded_steps(kind)

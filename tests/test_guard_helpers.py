@@ -1,6 +1,10 @@
 """tests/guard.py itself, on the CPU: the carved tensors equal the plain ones in every property a
 wrapper can see, and a write one element outside a tensor is found and named.  These are the
-detector's positive controls, so that no GPU test ever has to write out of bounds to show it works."""
+detector's positive controls, so that no GPU test ever has to write out of bounds to show it works.
+Every test runs twice: with the tensors' first byte on a 512-byte boundary, and (`*_at_skew_16`) 16
+bytes past one, the placement of tests/test_gpu_placement.py."""
+import functools
+
 import pytest
 import torch
 
@@ -8,7 +12,7 @@ import guard
 from guard import guarded, home
 
 BAND = 4096
-CPU = dict(band_bytes=BAND, devices=('cpu',))
+CPU = dict(band_bytes=BAND, devices=('cpu',), skew=0)      # at_skew_16 below sets the skew for a test
 
 
 def _make_all():
@@ -44,7 +48,7 @@ def test_carved_tensors_look_like_the_plain_ones_and_a_clean_block_verifies(patt
         got = carved[name]
         assert (got.shape, got.dtype, got.stride(), got.device) == (want.shape, want.dtype, want.stride(),
                                                                     want.device), name
-        assert got.data_ptr() % 512 == 0, name
+        assert got.numel() == 0 or got.data_ptr() % 512 == CPU['skew'], name     # no element: no address
         assert got.is_contiguous() == want.is_contiguous(), name
     storages = [t.untyped_storage().data_ptr() for t in carved.values()]
     assert len(set(storages)) == len(storages), 'one allocation per tensor'
@@ -129,7 +133,8 @@ def test_home_keeps_values_dtype_and_shape_and_its_trail_band_starts_at_the_next
         h = home(src, state, device='cpu')
         assert h.dtype == src.dtype and h.shape == src.shape and h.stride() == src.stride()
         n = src.numel()
-        assert torch.equal(h, src) and (n == 0 or h.data_ptr() != src.data_ptr()) and h.data_ptr() % 512 == 0
+        assert torch.equal(h, src)
+        assert n == 0 or (h.data_ptr() != src.data_ptr() and h.data_ptr() % 512 == CPU['skew'])
         flat = h.as_strided([n + 1], [1], h.storage_offset())
         band = flat[n:]
         if pattern == 'zero':
@@ -147,7 +152,7 @@ def test_home_keeps_values_dtype_and_shape_and_its_trail_band_starts_at_the_next
 
 
 def test_tensors_on_an_unlisted_device_pass_through_untouched():
-    with guarded('nan', band_bytes=BAND, devices=('cuda',)) as state:
+    with guarded('nan', band_bytes=BAND, devices=('cuda',), skew=CPU['skew']) as state:
         t = torch.empty([4, 4])
         m = torch.empty([4, 4], device='meta')
         like = torch.empty_like(t)
@@ -162,14 +167,60 @@ def test_what_cannot_be_rebuilt_is_returned_as_it_is_and_counted():
         s = torch.empty([2, 2], layout=torch.sparse_coo)
         t = torch.empty([2, 2])
     assert s.layout == torch.sparse_coo and s.shape == (2, 2)
-    assert state.unguarded == 1 and state.allocations == 1 and t.data_ptr() % 512 == 0
+    assert state.unguarded == 1 and state.allocations == 1 and t.data_ptr() % 512 == CPU['skew']
     state.verify()
 
 
 def test_band_bytes_must_be_a_multiple_of_512():
     with pytest.raises(AssertionError):
-        with guarded('zero', band_bytes=1000, devices=('cpu',)):
+        with guarded('zero', band_bytes=1000, devices=('cpu',), skew=CPU['skew']):
             pass
     with pytest.raises(AssertionError):
         with guarded('ones', **CPU):
             pass
+
+
+@pytest.mark.parametrize('skew', [8, 24, -16, 512, 528, 16.0])
+def test_skew_must_be_a_multiple_of_16_below_512(skew):
+    with pytest.raises(AssertionError, match='skew'):
+        with guarded('zero', band_bytes=BAND, devices=('cpu',), skew=skew):
+            pass
+
+
+@pytest.mark.parametrize('skew', [0, 16, 496])
+def test_the_first_byte_lies_skew_bytes_past_a_512_byte_boundary(skew):
+    """Carved tensors and home() alike, whatever the dtype; the bands still touch the tensor: a store
+    one byte before it and one byte after it are both named."""
+    with guarded('nan', band_bytes=BAND, devices=('cpu',), skew=skew) as state:
+        made = [victim(d, 5) for d in (torch.float32, torch.bfloat16, torch.int32, torch.uint8)]
+    made.append(home(torch.arange(35, dtype=torch.float32).view(5, 7).t(), state, device='cpu'))
+    assert made[-1].stride() == (1, 7)
+    for t in made:
+        assert t.data_ptr() % 512 == skew, (t.dtype, t.data_ptr() % 512)
+    state.verify()
+    b = made[3]                                            # uint8: one element is one byte
+    for at, name in ((-1, 'lead band'), (5, 'trail band')):
+        keep = _past(b, at).clone()
+        _past(b, at).fill_(9)
+        with pytest.raises(AssertionError, match=name):
+            state.verify()
+        _past(b, at).copy_(keep)
+        state.verify()
+
+
+def at_skew_16(test):
+    """`test` again with every guarded block of it at skew 16 (through CPU['skew'])."""
+    @functools.wraps(test)
+    def run(*args, **kwargs):
+        CPU['skew'] = 16
+        try:
+            return test(*args, **kwargs)
+        finally:
+            CPU['skew'] = 0
+    run.__name__ = run.__qualname__ = test.__name__ + '_at_skew_16'
+    return run
+
+
+for _name, _test in sorted(globals().items()):
+    if _name.startswith('test_') and callable(_test) and 'skew' not in _name:
+        globals()[_name + '_at_skew_16'] = at_skew_16(_test)

@@ -150,6 +150,17 @@ int spt_lookup_forward(const int32_t *query, const int32_t *key, int32_t *out,
                        int sparsity, void *stream);
 
 /*
+ * Grouped key/value heads: query [batch_size, S, M] with batch_size = N * heads, key
+ * [N * kv_heads, S, M]; slice n * heads + h reads the key codes of slice n * kv_heads +
+ * h / (heads / kv_heads).  The output is that of spt_lookup_forward on the key codes repeated per
+ * group.  A null pointer -> SPT_EINVAL; kv_heads <= 0, heads <= 0, heads % kv_heads != 0 or
+ * batch_size % heads != 0 -> SPT_ESHAPE, before any launch; everything else as above.
+ */
+int spt_lookup_forward_kv(const int32_t *query, const int32_t *key, int32_t *out,
+                          int batch_size, int seq_length, int n_subspaces, int sparsity,
+                          int heads, int kv_heads, void *stream);
+
+/*
  * sddmm_forward_cuda(trans_lhs=false, trans_rhs=true, indptr, indices, query, key)
  *   reference: extension/entry.cpp:27-31, extension/sddmm.cpp:3-73 (cusparseSDDMM)
  * out[b, p] = sum_e query[b, row(p), e] * key[b, indices[b, p], e];
@@ -375,6 +386,38 @@ int spt_attention_mfma_backward(const void *tiles, int layout, const float *q, c
                                 float *grad_q, float *grad_k, float *grad_v, int batch_size,
                                 int seq_length, int d_head, int nnz, float scale, float clamp,
                                 int heads, int transposed, void *stream);
+
+/*
+ * Grouped key/value heads (GQA / MQA checkpoints; no reference counterpart).  fp32, the
+ * [N, S, heads, E] head layout only.  q, y, grad_y, row_sum, bounds, delta, `tiles` and the grid stay
+ * per query slice (batch_size = N * heads); k and v are [N, S, kv_heads, E] and query head h reads
+ * kv head h / (heads / kv_heads) -- kv head j serves query heads j g .. j g + g - 1, g = heads /
+ * kv_heads (HuggingFace's repeat_kv order).  The arithmetic and its order are those of
+ * spt_attention_mfma_forward / _backward on k, v repeated g times along the head axis: y, row_sum,
+ * bounds and grad_q are the same bits.  The backward writes one PARTIAL of grad_k / grad_v per query
+ * head, [N, S, heads, E] each (again the bits of the repeated form); spt_head_group_sum adds the g
+ * partials of every kv head in ascending query-head order, ((p0 + p1) + p2) + ..., fp32, no atomics:
+ * parts [rows, heads, d_head] -> out [rows, kv_heads, d_head] (rows = N * S, or any multiple of it
+ * for buffers laid back to back).
+ * Preconditions, checked before any launch: a null pointer (bounds aside) -> SPT_EINVAL;
+ * kv_heads <= 0, heads <= 0, heads % kv_heads != 0 or batch_size % heads != 0 -> SPT_ESHAPE
+ * (spt_head_group_sum: also rows <= 0 or d_head % 4 != 0); everything else as the entries above.
+ * kv_heads == heads is accepted and is the call of the entries above.
+ */
+int spt_attention_mfma_forward_kv(const void *tiles, int layout, const float *q, const float *k,
+                                  const float *v, float *y, float *row_sum, float *bounds,
+                                  int batch_size, int seq_length, int d_head, int nnz, float scale,
+                                  float clamp, int heads, int kv_heads, int y_transposed,
+                                  void *stream);
+int spt_attention_mfma_backward_kv(const void *tiles, int layout, const float *q, const float *k,
+                                   const float *v, const float *y, const float *grad_y,
+                                   const float *row_sum, const float *bounds, float *delta,
+                                   float *grad_q, float *grad_k_parts, float *grad_v_parts,
+                                   int batch_size, int seq_length, int d_head, int nnz, float scale,
+                                   float clamp, int heads, int kv_heads, int transposed,
+                                   void *stream);
+int spt_head_group_sum(const float *parts, float *out, long long rows, int heads, int kv_heads,
+                       int d_head, void *stream);
 
 /*
  * bf16 STORAGE variants (BASELINE configs[1] "bf16"; no reference counterpart -- the reference is

@@ -290,7 +290,49 @@ __global__ __launch_bounds__(MB_WAVES * SPT_WAVE) void attention_cell_bits_kerne
     }
 }
 
+// ---- grouped key/value heads: the fixed-order sum of the key-owned kernel's partials ----
+// parts [rows, heads, E] (one partial of grad_k / grad_v per QUERY head, as the key-owned kernel
+// writes them) -> out [rows, kv_heads, E]: out[r, j] = ((p[r, j g] + p[r, j g + 1]) + p[r, j g + 2]) + ...
+// over the g = heads / kv_heads query heads of kv head j, ascending, plain fp32 adds -- the same bits
+// on every run.  A thread owns one float4 of the output; a row's partials are g runs of E floats E
+// apart, so consecutive threads read consecutive 16 bytes.
+__global__ __launch_bounds__(256) void head_group_sum_kernel(const float4 *__restrict__ parts,
+                                                             float4 *__restrict__ out, long long n4,
+                                                             int e4, int group) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const long long slot = i / e4;                      // (row, kv head)
+    const int c = (int)(i - slot * e4);
+    const float4 *p = parts + slot * group * e4 + c;
+    float4 acc = p[0];
+    for (int u = 1; u < group; u++) {
+        const float4 x = p[(long long)u * e4];
+        acc.x += x.x;
+        acc.y += x.y;
+        acc.z += x.z;
+        acc.w += x.w;
+    }
+    out[i] = acc;
+}
+
 }  // namespace spt
+
+extern "C" int spt_head_group_sum(const float *parts, float *out, long long rows, int heads,
+                                  int kv_heads, int d_head, void *stream) {
+    using namespace spt;
+    if (!parts || !out) return SPT_EINVAL;
+    if (heads <= 0 || kv_heads <= 0 || heads % kv_heads != 0) return SPT_ESHAPE;
+    if (rows <= 0 || d_head <= 0 || d_head % 4 != 0) return SPT_ESHAPE;
+    const int e4 = d_head / 4;
+    const long long n4 = rows * kv_heads * e4;
+    const long long blocks = (n4 + 255) / 256;
+    if (blocks > 0x7FFFFFFFLL) return SPT_EUNSUP;
+    hipLaunchKernelGGL(head_group_sum_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const float4 *>(parts),
+                       reinterpret_cast<float4 *>(out), n4, e4, heads / kv_heads);
+    SPT_LAUNCH_CHECK();
+    return SPT_OK;
+}
 
 extern "C" int spt_attention_mfma_supported(int seq_length, int d_head, int nnz) {
     return spt::mfma_shape_ok(seq_length, d_head, nnz) ? 1 : 0;

@@ -308,10 +308,20 @@ __device__ __forceinline__ void lookup_row(const uint32_t *__restrict__ kcodes,
     __builtin_amdgcn_wave_barrier();
 }
 
+// Grouped key/value heads: the key codes are [N * kv_heads, S, M] and query slice b = n * heads + h
+// reads the codes of kv slice n * kv_heads + h / kv_group (kv_group = heads / kv_heads query heads
+// per kv head, consecutive).  kv_group == 1: the slice itself.
+__device__ __forceinline__ int kv_slice(int b, int heads, int kv_group) {
+    if (kv_group == 1) return b;                        // (uniform: no division without groups)
+    const int n = b / heads, h = b - n * heads;
+    return n * (heads / kv_group) + h / kv_group;
+}
+
 template <int WN, int WU, int LANES>  // words per token (nibble, uint16 form); lanes per row
 __global__ __launch_bounds__(LK_THREADS) void lookup_forward_kernel(
     const int32_t *__restrict__ query, const int32_t *__restrict__ key,
-    int32_t *__restrict__ out, int B, int S, int M, int Z, int tiles_per_batch) {
+    int32_t *__restrict__ out, int B, int S, int M, int Z, int tiles_per_batch, int heads,
+    int kv_group) {
     constexpr int RPW = SPT_WAVE / LANES;   // rows per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint32_t *kcodes = reinterpret_cast<uint32_t *>(smem);                 // [cols][W]
@@ -325,7 +335,7 @@ __global__ __launch_bounds__(LK_THREADS) void lookup_forward_kernel(
     const int tile = tiles_per_batch - 1 - (blockIdx.x / B);
     const int row0 = tile * LK_ROWS;
     const int ncols = row0 + LK_ROWS;  // columns any row of this block may look at
-    const int32_t *ksrc = key + (size_t)b * S * M;
+    const int32_t *ksrc = key + (size_t)kv_slice(b, heads, kv_group) * S * M;
     const int32_t *qsrc = query + ((size_t)b * S + row0) * M;
 
     // ---- can this block use the 4-bit form?  (all codes it touches in [0, 16)) --------
@@ -400,7 +410,7 @@ template <int W>
 __global__ __launch_bounds__(LR_THREADS) void lookup_rows_kernel(
     const int32_t *__restrict__ query, const int32_t *__restrict__ key,
     int32_t *__restrict__ out, int B, int S, int M, int Z, int blocks_per_batch, int list_pitch,
-    int out_pitch) {
+    int out_pitch, int heads, int kv_group) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & (SPT_WAVE - 1);
     // The four workers' lists are independent until the final fix-up, so the block's waves
@@ -424,7 +434,7 @@ __global__ __launch_bounds__(LR_THREADS) void lookup_rows_kernel(
         smem + kbytes + (size_t)SPT_WAVE * list_pitch);   // [64][out_pitch]
     unsigned *xch = reinterpret_cast<unsigned *>(
         smem + kbytes + (size_t)SPT_WAVE * list_pitch + (size_t)SPT_WAVE * out_pitch * 2);  // [64][2]
-    const int32_t *ksrc = key + (size_t)b * S * M;
+    const int32_t *ksrc = key + (size_t)kv_slice(b, heads, kv_group) * S * M;
     const int32_t *qsrc = query + ((size_t)b * S + min(gy, S - 1)) * M;
 
     // 4-bit form unless some code this block touches is outside [0, 16).  One pass: every lane
@@ -644,7 +654,7 @@ template <int W>
 __global__ __launch_bounds__(256) void lookup_rows_long_kernel(
     const int32_t *__restrict__ query, const int32_t *__restrict__ key,
     int32_t *__restrict__ out, int B, int S, int M, int Z, int blocks_per_batch, int GP,
-    int out_pitch) {
+    int out_pitch, int heads, int kv_group) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & (SPT_WAVE - 1);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // = the worker (column mod 4)
@@ -660,7 +670,7 @@ __global__ __launch_bounds__(256) void lookup_rows_long_kernel(
     unsigned short *lastg_all = orow + (size_t)SPT_WAVE * out_pitch;              // [64][2][4]
     unsigned long long *xch = reinterpret_cast<unsigned long long *>(
         smem + kbytes + (size_t)SPT_WAVE * out_pitch * 2 + (size_t)SPT_WAVE * 16);   // [64][2]
-    const int32_t *ksrc = key + (size_t)b * S * M;
+    const int32_t *ksrc = key + (size_t)kv_slice(b, heads, kv_group) * S * M;
     const int32_t *qsrc = query + ((size_t)b * S + min(gy, S - 1)) * M;
 
     // the block's output rows start as zeros (lookup.cu:107-109)
@@ -867,9 +877,10 @@ __global__ __launch_bounds__(256) void lookup_rows_long_kernel(
 
 using namespace spt;
 
-extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int32_t *out,
-                                  int batch_size, int seq_length, int n_subspaces,
-                                  int sparsity, void *stream) {
+// heads / kv_group: see kv_slice (1 / 1: every slice reads its own key codes)
+static int lookup_forward_any(const int32_t *query, const int32_t *key, int32_t *out,
+                              int batch_size, int seq_length, int n_subspaces, int sparsity,
+                              int heads, int kv_group, void *stream) {
     if (!query || !key || !out) return SPT_EINVAL;
     if (batch_size <= 0 || seq_length <= 0 || n_subspaces <= 0 || sparsity <= 0)
         return SPT_EINVAL;
@@ -895,11 +906,11 @@ extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int3
             if (WN == 1)
                 hipLaunchKernelGGL(lookup_rows_kernel<1>, dim3((unsigned)nblk), dim3(LR_THREADS), lds,
                                    s, query, key, out, batch_size, S, M, Z, nb, list_pitch,
-                                   out_pitch);
+                                   out_pitch, heads, kv_group);
             else
                 hipLaunchKernelGGL(lookup_rows_kernel<2>, dim3((unsigned)nblk), dim3(LR_THREADS), lds,
                                    s, query, key, out, batch_size, S, M, Z, nb, list_pitch,
-                                   out_pitch);
+                                   out_pitch, heads, kv_group);
             SPT_LAUNCH_CHECK();
             return SPT_OK;
         }
@@ -916,10 +927,12 @@ extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int3
         if (lds <= 64 * 1024 && nblk <= 0x7FFFFFFFLL) {
             if (WN == 1)
                 hipLaunchKernelGGL(lookup_rows_long_kernel<1>, dim3((unsigned)nblk), dim3(256), lds, s,
-                                   query, key, out, batch_size, S, M, Z, nb, GP, out_pitch);
+                                   query, key, out, batch_size, S, M, Z, nb, GP, out_pitch, heads,
+                                   kv_group);
             else
                 hipLaunchKernelGGL(lookup_rows_long_kernel<2>, dim3((unsigned)nblk), dim3(256), lds, s,
-                                   query, key, out, batch_size, S, M, Z, nb, GP, out_pitch);
+                                   query, key, out, batch_size, S, M, Z, nb, GP, out_pitch, heads,
+                                   kv_group);
             SPT_LAUNCH_CHECK();
             return SPT_OK;
         }
@@ -939,7 +952,8 @@ extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int3
                 reinterpret_cast<const void *>(&lookup_forward_kernel<WN_, WU_, LN_>),        \
                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                       \
         hipLaunchKernelGGL((lookup_forward_kernel<WN_, WU_, LN_>), grid, dim3(LK_THREADS),    \
-                           lds, s, query, key, out, batch_size, S, M, Z, tiles);              \
+                           lds, s, query, key, out, batch_size, S, M, Z, tiles, heads,       \
+                           kv_group);                                                         \
     } while (0)
 #define SPT_LK(WN_, WU_)                                    \
     do {                                                    \
@@ -960,4 +974,21 @@ extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int3
 #undef SPT_LK
     SPT_LAUNCH_CHECK();
     return SPT_OK;
+}
+
+extern "C" int spt_lookup_forward(const int32_t *query, const int32_t *key, int32_t *out,
+                                  int batch_size, int seq_length, int n_subspaces,
+                                  int sparsity, void *stream) {
+    return lookup_forward_any(query, key, out, batch_size, seq_length, n_subspaces, sparsity, 1, 1,
+                              stream);
+}
+
+extern "C" int spt_lookup_forward_kv(const int32_t *query, const int32_t *key, int32_t *out,
+                                     int batch_size, int seq_length, int n_subspaces,
+                                     int sparsity, int heads, int kv_heads, void *stream) {
+    if (!query || !key || !out) return SPT_EINVAL;
+    if (heads <= 0 || kv_heads <= 0) return SPT_ESHAPE;
+    if (heads % kv_heads != 0 || batch_size <= 0 || batch_size % heads != 0) return SPT_ESHAPE;
+    return lookup_forward_any(query, key, out, batch_size, seq_length, n_subspaces, sparsity, heads,
+                              heads / kv_heads, stream);
 }

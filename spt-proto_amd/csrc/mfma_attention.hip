@@ -157,12 +157,15 @@ __device__ __forceinline__ float exact_dot(const T *a, const T *b) {
 // duration of the loop -- a hand-placed spill, paid only inside the rare branch.
 constexpr int MA_PARK = 32 * SPT_WAVE * 4;          // bytes per wave: d and dp, [register][lane]
 // own: the own operand's slice base (rows of `ld` elements), own_row0: the wave's first own row
-// (lane & 31 is added here); tile_rows: the streamed operand's tile; park0: the parking blocks'
-// base (the wave's block is chosen here).  Everything lane-dependent is derived from rare_lane().
+// (lane & 31 is added here); tile_rows: the streamed operand's tile (rows of `ld_tile` elements: with
+// grouped key/value heads one of the two operands is K, whose rows are narrower than Q's); park0: the
+// parking blocks' base (the wave's block is chosen here).  Everything lane-dependent is derived from
+// rare_lane().
 template <typename T>
 __device__ __forceinline__ void clamp_exact(f32x16 &d, f32x16 &dp, char *park0, int wave, const uint4 &cw,
                                             float bound, float thr, const T *own, int own_row0, int S,
-                                            const T *tile_rows, int ld, float scale, float clampv) {
+                                            const T *tile_rows, int ld, int ld_tile, float scale,
+                                            float clampv) {
     const unsigned w[4] = {cw.x, cw.y, cw.z, cw.w};
     const float eps = bound - thr;
     unsigned near = 0, in = 0;
@@ -182,7 +185,7 @@ __device__ __forceinline__ void clamp_exact(f32x16 &d, f32x16 &dp, char *park0, 
     const T *own_row = own + (size_t)min(own_row0 + (lane & 31), S - 1) * ld;
     for (unsigned rem = near; rem != 0u; rem &= rem - 1u) {
         const int r = __builtin_ctz(rem);
-        const float sc = exact_dot(own_row, tile_rows + (size_t)acc_row(r, lane >> 5) * ld) * scale;
+        const float sc = exact_dot(own_row, tile_rows + (size_t)acc_row(r, lane >> 5) * ld_tile) * scale;
         if (fabsf(sc) < clampv) in |= 1u << r;
     }
     asm volatile("" ::: "memory");
@@ -224,7 +227,7 @@ void attention_mfma_forward_kernel(
     const unsigned char *__restrict__ pool, const unsigned *__restrict__ sat,
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
     T *__restrict__ y, float *__restrict__ row_sum, float *__restrict__ bounds, int S, float scale,
-    float clampv, int heads, int blocks_per_batch) {
+    float clampv, int heads, int kv_heads, int blocks_per_batch) {
     constexpr int PI = Elem<T>::PARTS;                  // parts of the K / V images
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *img = smem;                                   // [2][MA_IMG]
@@ -236,8 +239,11 @@ void attention_mfma_forward_kernel(
     const int b = bid / blocks_per_batch;
     const int i0 = MA_WROWS * folded_row_tile(bid % blocks_per_batch, blocks_per_batch, wave);
     const DenseView dv = dense_view(b, S, MA_E, heads);
+    // K and V alone: the kv head's slice (fp32; the bf16-storage entries have no grouped form)
+    DenseView kv = dv;
+    if constexpr (sizeof(T) == 4) kv = kv_view(b, S, MA_E, heads, kv_heads);
     const int RT = (S + MA_WROWS - 1) / MA_WROWS;
-    const T *k_b = k + dv.base, *v_b = v + dv.base;
+    const T *k_b = k + kv.base, *v_b = v + kv.base;
 
     const CellTiles ct(masks, cells, pool, sat, b, RT, i0 / MA_WROWS, i0 < S);
     // tiles any row of this workgroup can see: keys <= its last row (that of wave 7)
@@ -245,7 +251,7 @@ void attention_mfma_forward_kernel(
     const int T_ = min(RT, last_tile + 1);
     const ScoreMap sm(scale, clampv);
     // every prologue load is issued before the first result is needed
-    const TileStager<T> stager(k_b, v_b, dv.ld, S, tid);
+    const TileStager<T> stager(k_b, v_b, kv.ld, S, tid);
     TileRegs<T> nxt = stager.load(0);
     uint4 mcur = ct.load(0, lane), mnxt;
     Frag qf[MA_KS];
@@ -490,8 +496,8 @@ void attention_mfma_backward_rows_kernel(
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
     const T *__restrict__ gy, const T *__restrict__ y,
     const float *__restrict__ row_sum, const float *__restrict__ bounds, T *__restrict__ grad_q,
-    float *__restrict__ delta, int S, float scale, float clampv, int heads, int blocks_per_batch,
-    int half) {
+    float *__restrict__ delta, int S, float scale, float clampv, int heads, int kv_heads,
+    int blocks_per_batch, int half) {
     constexpr int PI = Elem<T>::PARTS;                  // parts of the K / V images
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *img = smem;                                   // [2][MA_IMG]
@@ -501,12 +507,15 @@ void attention_mfma_backward_rows_kernel(
     const BwBlock blk = bw_block(blocks_per_batch, wave, true);
     const int b = blk.b;
     const DenseView dv = dense_view(b, S, MA_E, heads);
+    // K and V alone: the kv head's slice (fp32; the bf16-storage entries have no grouped form)
+    DenseView kv = dv;
+    if constexpr (sizeof(T) == 4) kv = kv_view(b, S, MA_E, heads, kv_heads);
     const int RT = (S + MA_WROWS - 1) / MA_WROWS;
     const ScoreMap sm(scale, clampv);
     const int i0 = MA_WROWS * blk.tile;
     const CellTiles ct(masks, cells, pool, sat, b, RT, i0 / MA_WROWS, i0 < S);
     const int T_ = min(RT, blk.last + 1);
-    const TileStager<T, BW_THREADS> stager(k + dv.base, v + dv.base, dv.ld, S, tid);
+    const TileStager<T, BW_THREADS> stager(k + kv.base, v + kv.base, kv.ld, S, tid);
     TileRegs<T, BW_THREADS> nxt = stager.load(0);
     uint4 mcur = ct.load(0, lane), mnxt;
     // own rows: dY (B operand of dP = V dY^T), delta = max(1e-9, dY . Y), Q (B operand of D)
@@ -580,7 +589,7 @@ void attention_mfma_backward_rows_kernel(
             const uint4 cw = ct.words(mcur, t, lane);
             if (cg.wanted(d))                           // (wave-uniform, rare)
                 clamp_exact(d, dp, smem + 2 * MA_IMG, wave, cw, sm.bound, cg.thr, q + dv.base, i0, S,
-                            k + dv.base + (size_t)t * MA_KT * dv.ld, dv.ld, scale, clampv);
+                            k + kv.base + (size_t)t * MA_KT * kv.ld, dv.ld, kv.ld, scale, clampv);
             const unsigned mw[4] = {cw.x, cw.y, cw.z, cw.w};
             float ds[16];
 #pragma unroll
@@ -726,7 +735,7 @@ void attention_mfma_backward_keys_kernel(
     const T *__restrict__ q, const T *__restrict__ k, const T *__restrict__ v,
     const T *__restrict__ gy, const float *__restrict__ row_sum, const float *__restrict__ bounds,
     const float *__restrict__ delta, T *__restrict__ grad_k, T *__restrict__ grad_v,
-    int S, float scale, float clampv, int heads, int blocks_per_batch, int half) {
+    int S, float scale, float clampv, int heads, int kv_heads, int blocks_per_batch, int half) {
     constexpr int PI = Elem<T>::PARTS;                  // parts of the Q image and of the V fragments
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *img = smem;                                   // [2][MK_IMG]
@@ -738,6 +747,10 @@ void attention_mfma_backward_keys_kernel(
     const int kt = blk.tile;
     const int j0 = kt * MA_KT;
     const DenseView dv = dense_view(b, S, MA_E, heads);
+    // K and V are READ from the kv head's slice; grad_k and grad_v are WRITTEN per query slice (dv):
+    // with grouped heads they are this query head's partials, summed by head_group_sum_kernel
+    DenseView kv = dv;                                  // (fp32 only: bf16 storage has no grouped form)
+    if constexpr (sizeof(T) == 4) kv = kv_view(b, S, MA_E, heads, kv_heads);
     const int RT = (S + MA_WROWS - 1) / MA_WROWS;
     const bool have = j0 < S;
 
@@ -748,7 +761,7 @@ void attention_mfma_backward_keys_kernel(
     float k2 = 0.f;
     {
         float xk[MA_E / 2];
-        load_own_rows_raw(xk, k + dv.base, dv.ld, S, j0, lane);
+        load_own_rows_raw(xk, k + kv.base, kv.ld, S, j0, lane);
         if (WANT_K && bounds) {
 #pragma unroll
             for (int x = 0; x < MA_E / 2; x++) k2 = fmaf(xk[x], xk[x], k2);
@@ -757,7 +770,7 @@ void attention_mfma_backward_keys_kernel(
         split_own_rows(kf, xk, sm.sl2);     // the score scale (log2 domain) folded into K
         if constexpr (WANT_K) {             // V only feeds dP, which only dS needs
             float xv[MA_E / 2];
-            load_own_rows_raw(xv, v + dv.base, dv.ld, S, j0, lane);
+            load_own_rows_raw(xv, v + kv.base, kv.ld, S, j0, lane);
             split_own_rows(vf, xv);         // (stored bf16: the lo parts are zero and unused)
         }
     }
@@ -854,8 +867,8 @@ void attention_mfma_backward_keys_kernel(
             const uint4 cw = cell_words(mcur, mlt, lane);
             if constexpr (WANT_K) {
                 if (cg.wanted(d))                       // (wave-uniform, rare)
-                    clamp_exact(d, dp, smem + 2 * MK_IMG, wave, cw, sm.bound, cg.thr, k + dv.base, j0, S,
-                                q + dv.base + (size_t)rt * MA_WROWS * dv.ld, dv.ld, scale, clampv);
+                    clamp_exact(d, dp, smem + 2 * MK_IMG, wave, cw, sm.bound, cg.thr, k + kv.base, j0, S,
+                                q + dv.base + (size_t)rt * MA_WROWS * dv.ld, kv.ld, dv.ld, scale, clampv);
             }
             const float *st = reinterpret_cast<const float *>(buf + MK_ST);
             const unsigned mw[4] = {cw.x, cw.y, cw.z, cw.w};
@@ -942,7 +955,8 @@ template <typename T>
 static int launch_forward_t(const unsigned long long *masks, const unsigned char *cells,
                             const unsigned char *pool, const unsigned *sat, const T *q, const T *k,
                             const T *v, T *y, float *row_sum, float *bounds, int batch_size, int S,
-                            float scale, float clamp, int heads, int y_transposed, hipStream_t s) {
+                            float scale, float clamp, int heads, int kv_heads, int y_transposed,
+                            hipStream_t s) {
     const int bpb = (S + MA_ROWS - 1) / MA_ROWS;
     const size_t lds = mfma_forward_lds();
     const dim3 grid((unsigned)batch_size * bpb), block(MA_THREADS);
@@ -951,7 +965,8 @@ static int launch_forward_t(const unsigned long long *masks, const unsigned char
         SPT_HIP_TRY(hipFuncSetAttribute((const void *)attention_mfma_forward_kernel<T, YT>,      \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
         hipLaunchKernelGGL((attention_mfma_forward_kernel<T, YT>), grid, block, lds, s, masks, cells, pool, \
-                           sat, q, k, v, y, row_sum, bounds, S, scale, clamp, heads, bpb);       \
+                           sat, q, k, v, y, row_sum, bounds, S, scale, clamp, heads, kv_heads,   \
+                           bpb);                                                                 \
     } while (0)
     if (y_transposed) SPT_MF(true); else SPT_MF(false);
 #undef SPT_MF
@@ -966,7 +981,7 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
                              const T *v, const T *y, const T *grad_y, const float *row_sum,
                              const float *bounds, float *delta, T *grad_q, T *grad_k, T *grad_v,
                              int batch_size, int S, float scale, float clamp, int heads,
-                             int transposed, hipStream_t s) {
+                             int kv_heads, int transposed, hipStream_t s) {
     const int bpb = (S + BW_ROWS - 1) / BW_ROWS;
     const dim3 grid((unsigned)batch_size * bpb), block(BW_THREADS);
     const size_t lds_r = 2 * MA_IMG + (size_t)BW_WAVES * MA_PARK,
@@ -981,7 +996,7 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
         for (int half = 0; half < MA_ET / MR_QTILES; half++)                                    \
             hipLaunchKernelGGL((attention_mfma_backward_rows_kernel<T, GT>), grid, block, lds_r, \
                                s, masks, cells, pool, sat, q, k, v, grad_y, y, row_sum, bounds, \
-                               grad_q, delta, S, scale, clamp, heads, bpb, half);               \
+                               grad_q, delta, S, scale, clamp, heads, kv_heads, bpb, half);     \
         if constexpr (MK_FUSED) {                                                               \
             SPT_KEYS(GT, 0, 0);                                                                 \
         } else {                                                                                \
@@ -996,7 +1011,8 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k));                           \
         hipLaunchKernelGGL((attention_mfma_backward_keys_kernel<T, GT, MODE>), grid, block, \
                            lds_k, s, masks, cells_t, pool_t, sat, q, k, v, grad_y, row_sum,     \
-                           bounds, delta, grad_k, grad_v, S, scale, clamp, heads, bpb, HALF);   \
+                           bounds, delta, grad_k, grad_v, S, scale, clamp, heads, kv_heads,     \
+                           bpb, HALF);                                                          \
     } while (0)
     if (transposed) SPT_MB(true);
     else SPT_MB(false);
@@ -1009,15 +1025,15 @@ static int launch_backward_t(const unsigned long long *masks, const unsigned cha
 int launch_forward(const unsigned long long *masks, const unsigned char *cells,
                    const unsigned char *pool, const unsigned *sat, int dtype, const void *q,
                    const void *k, const void *v, void *y, float *row_sum, float *bounds,
-                   int batch_size, int S, float scale, float clamp, int heads, int y_transposed,
-                   hipStream_t s) {
+                   int batch_size, int S, float scale, float clamp, int heads, int kv_heads,
+                   int y_transposed, hipStream_t s) {
     if (dtype == SPT_BF16)
         return launch_forward_t<bf16_t>(masks, cells, pool, sat, (const bf16_t *)q, (const bf16_t *)k,
                                         (const bf16_t *)v, (bf16_t *)y, row_sum, bounds, batch_size, S,
-                                        scale, clamp, heads, y_transposed, s);
+                                        scale, clamp, heads, kv_heads, y_transposed, s);
     return launch_forward_t<float>(masks, cells, pool, sat, (const float *)q, (const float *)k,
                                    (const float *)v, (float *)y, row_sum, bounds, batch_size, S, scale,
-                                   clamp, heads, y_transposed, s);
+                                   clamp, heads, kv_heads, y_transposed, s);
 }
 
 int launch_backward(const unsigned long long *masks, const unsigned char *cells,
@@ -1026,18 +1042,18 @@ int launch_backward(const unsigned long long *masks, const unsigned char *cells,
                     const void *k, const void *v, const void *y, const void *grad_y,
                     const float *row_sum, const float *bounds, float *delta, void *grad_q,
                     void *grad_k, void *grad_v, int batch_size, int S, float scale, float clamp,
-                    int heads, int transposed, hipStream_t s) {
+                    int heads, int kv_heads, int transposed, hipStream_t s) {
     if (dtype == SPT_BF16)
         return launch_backward_t<bf16_t>(masks, cells, cells_t, pool, pool_t, sat, (const bf16_t *)q,
                                          (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)y,
                                          (const bf16_t *)grad_y, row_sum, bounds, delta,
                                          (bf16_t *)grad_q, (bf16_t *)grad_k, (bf16_t *)grad_v,
-                                         batch_size, S, scale, clamp, heads, transposed, s);
+                                         batch_size, S, scale, clamp, heads, kv_heads, transposed, s);
     return launch_backward_t<float>(masks, cells, cells_t, pool, pool_t, sat, (const float *)q,
                                     (const float *)k, (const float *)v, (const float *)y,
                                     (const float *)grad_y, row_sum, bounds, delta, (float *)grad_q,
                                     (float *)grad_k, (float *)grad_v, batch_size, S, scale, clamp,
-                                    heads, transposed, s);
+                                    heads, kv_heads, transposed, s);
 }
 
 MA_NS_CLOSE
@@ -1046,7 +1062,7 @@ MA_NS_CLOSE
 static int mfma_forward_any(const void *tiles, int layout, int dtype, const void *q,
                             const void *k, const void *v, void *y, float *row_sum, float *bounds,
                             int batch_size, int seq_length, int d_head, int nnz, float scale,
-                            float clamp, int heads, int y_transposed, void *stream) {
+                            float clamp, int heads, int kv_heads, int y_transposed, void *stream) {
     using namespace spt;
     if (!tiles || !q || !k || !v || !y || !row_sum) return SPT_EINVAL;
     if (batch_size <= 0 || heads < 0) return SPT_EINVAL;
@@ -1057,15 +1073,15 @@ static int mfma_forward_any(const void *tiles, int layout, int dtype, const void
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto fwd = d_head == 64 ? launch_forward : d_head == 80 ? e80::launch_forward : e128::launch_forward;
     return fwd(ts.masks, ts.cells, ts.pool, ts.sat, dtype, q, k, v, y, row_sum, bounds, batch_size,
-               seq_length, scale, clamp, heads, y_transposed, s);
+               seq_length, scale, clamp, heads, kv_heads, y_transposed, s);
 }
 
 static int mfma_backward_any(const void *tiles, int layout, int dtype, const void *q,
                              const void *k, const void *v, const void *y, const void *grad_y,
                              const float *row_sum, const float *bounds, float *delta, void *grad_q,
                              void *grad_k, void *grad_v, int batch_size, int seq_length, int d_head,
-                             int nnz, float scale, float clamp, int heads, int transposed,
-                             void *stream) {
+                             int nnz, float scale, float clamp, int heads, int kv_heads,
+                             int transposed, void *stream) {
     using namespace spt;
     if (!tiles || !q || !k || !v || !y || !grad_y || !row_sum || !delta || !grad_q || !grad_k ||
         !grad_v)
@@ -1080,7 +1096,7 @@ static int mfma_backward_any(const void *tiles, int layout, int dtype, const voi
     auto bwd = d_head == 64 ? launch_backward : d_head == 80 ? e80::launch_backward : e128::launch_backward;
     return bwd(ts.masks, ts.cells, ts.cells_t, ts.pool, ts.pool_t, ts.sat, dtype, q, k, v, y, grad_y,
                row_sum, bounds, delta, grad_q, grad_k, grad_v, batch_size, seq_length, scale, clamp,
-               heads, transposed, s);
+               heads, kv_heads, transposed, s);
 }
 
 extern "C" int spt_attention_mfma_forward(const void *tiles, int layout, const float *q,
@@ -1089,7 +1105,7 @@ extern "C" int spt_attention_mfma_forward(const void *tiles, int layout, const f
                                           int seq_length, int d_head, int nnz, float scale,
                                           float clamp, int heads, int y_transposed, void *stream) {
     return mfma_forward_any(tiles, layout, SPT_F32, q, k, v, y, row_sum, bounds, batch_size,
-                            seq_length, d_head, nnz, scale, clamp, heads, y_transposed, stream);
+                            seq_length, d_head, nnz, scale, clamp, heads, heads, y_transposed, stream);
 }
 
 extern "C" int spt_attention_mfma_backward(const void *tiles, int layout, const float *q,
@@ -1101,7 +1117,46 @@ extern "C" int spt_attention_mfma_backward(const void *tiles, int layout, const 
                                            float clamp, int heads, int transposed, void *stream) {
     return mfma_backward_any(tiles, layout, SPT_F32, q, k, v, y, grad_y, row_sum, bounds, delta,
                              grad_q, grad_k, grad_v, batch_size, seq_length, d_head, nnz, scale,
-                             clamp, heads, transposed, stream);
+                             clamp, heads, heads, transposed, stream);
+}
+
+// Grouped key/value heads (fp32, [N, S, heads, E] layout only): k, v [N, S, kv_heads, E]; the
+// backward's grad_k / grad_v are the per-QUERY-head partials [N, S, heads, E] (spt_head_group_sum
+// reduces them).  Refusals before any launch.
+static int kv_heads_ok(int batch_size, int heads, int kv_heads) {
+    if (heads <= 0 || kv_heads <= 0) return SPT_ESHAPE;
+    if (heads % kv_heads != 0 || batch_size <= 0 || batch_size % heads != 0) return SPT_ESHAPE;
+    return SPT_OK;
+}
+
+extern "C" int spt_attention_mfma_forward_kv(const void *tiles, int layout, const float *q,
+                                             const float *k, const float *v, float *y,
+                                             float *row_sum, float *bounds, int batch_size,
+                                             int seq_length, int d_head, int nnz, float scale,
+                                             float clamp, int heads, int kv_heads,
+                                             int y_transposed, void *stream) {
+    if (!tiles || !q || !k || !v || !y || !row_sum) return SPT_EINVAL;
+    if (const int rc = kv_heads_ok(batch_size, heads, kv_heads)) return rc;
+    return mfma_forward_any(tiles, layout, SPT_F32, q, k, v, y, row_sum, bounds, batch_size,
+                            seq_length, d_head, nnz, scale, clamp, heads, kv_heads, y_transposed,
+                            stream);
+}
+
+extern "C" int spt_attention_mfma_backward_kv(const void *tiles, int layout, const float *q,
+                                              const float *k, const float *v, const float *y,
+                                              const float *grad_y, const float *row_sum,
+                                              const float *bounds, float *delta, float *grad_q,
+                                              float *grad_k_parts, float *grad_v_parts,
+                                              int batch_size, int seq_length, int d_head, int nnz,
+                                              float scale, float clamp, int heads, int kv_heads,
+                                              int transposed, void *stream) {
+    if (!tiles || !q || !k || !v || !y || !grad_y || !row_sum || !delta || !grad_q ||
+        !grad_k_parts || !grad_v_parts)
+        return SPT_EINVAL;
+    if (const int rc = kv_heads_ok(batch_size, heads, kv_heads)) return rc;
+    return mfma_backward_any(tiles, layout, SPT_F32, q, k, v, y, grad_y, row_sum, bounds, delta,
+                             grad_q, grad_k_parts, grad_v_parts, batch_size, seq_length, d_head, nnz,
+                             scale, clamp, heads, kv_heads, transposed, stream);
 }
 
 extern "C" int spt_attention_mfma_forward_bf16(const void *tiles, int layout, const uint16_t *q,
@@ -1111,7 +1166,7 @@ extern "C" int spt_attention_mfma_forward_bf16(const void *tiles, int layout, co
                                                float clamp, int heads, int y_transposed,
                                                void *stream) {
     return mfma_forward_any(tiles, layout, SPT_BF16, q, k, v, y, row_sum, bounds, batch_size,
-                            seq_length, d_head, nnz, scale, clamp, heads, y_transposed, stream);
+                            seq_length, d_head, nnz, scale, clamp, heads, heads, y_transposed, stream);
 }
 
 extern "C" int spt_attention_mfma_backward_bf16(const void *tiles, int layout, const uint16_t *q,
@@ -1124,6 +1179,6 @@ extern "C" int spt_attention_mfma_backward_bf16(const void *tiles, int layout, c
                                                 int heads, int transposed, void *stream) {
     return mfma_backward_any(tiles, layout, SPT_BF16, q, k, v, y, grad_y, row_sum, bounds, delta,
                              grad_q, grad_k, grad_v, batch_size, seq_length, d_head, nnz, scale,
-                             clamp, heads, transposed, stream);
+                             clamp, heads, heads, transposed, stream);
 }
 #endif

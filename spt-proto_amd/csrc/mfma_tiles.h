@@ -156,21 +156,23 @@ inline TileSet carve_tiles(void *ws, int B, int S, int layout) {
 
 // ---- launchers: one set per d_head, in spt (64), spt::e128 and spt::e80 ----
 // dtype: SPT_F32 (float tensors) or SPT_BF16 (bf16 storage; row_sum and delta stay fp32).
+// kv_heads: heads of k and v ([N, S, kv_heads, E]; == heads unless the heads are grouped -- then
+// grad_k / grad_v are per-query-head partials [N, S, heads, E], see spt_common.h kv_view).
 // (launch_spmm_mfma is defined for d_head 64 and 128 only: spmm_mfma.hip.)
 #define MA_DECLARE_LAUNCHERS                                                                      \
     int launch_forward(const unsigned long long *masks, const unsigned char *cells,               \
                        const unsigned char *pool, const unsigned *sat, int dtype, const void *q,  \
                        const void *k, const void *v, void *y, float *row_sum, float *bounds,      \
                        int batch_size, int S, float scale, float clamp, int heads,                \
-                       int y_transposed, hipStream_t s);                                          \
+                       int kv_heads, int y_transposed, hipStream_t s);                            \
     int launch_backward(const unsigned long long *masks, const unsigned char *cells,              \
                         const unsigned char *cells_t, const unsigned char *pool,                  \
                         const unsigned char *pool_t, const unsigned *sat, int dtype,              \
                         const void *q, const void *k, const void *v, const void *y,               \
                         const void *grad_y, const float *row_sum, const float *bounds,            \
                         float *delta, void *grad_q, void *grad_k, void *grad_v, int batch_size,   \
-                        int S, float scale, float clamp, int heads, int transposed,               \
-                        hipStream_t s);                                                           \
+                        int S, float scale, float clamp, int heads, int kv_heads,                 \
+                        int transposed, hipStream_t s);                                           \
     int launch_spmm_mfma(const int32_t *indptr, const int32_t *indices, const float *values,      \
                          const float *x, float *y, int B, int S, int nnz, int x_heads,            \
                          int y_heads, hipStream_t s);

@@ -135,6 +135,19 @@ __device__ __forceinline__ DenseView dense_view(int b, int S, int E, int heads) 
     return v;
 }
 
+// Grouped key/value heads: K and V live in an [N, S, kv_heads, E] tensor and query slice
+// b = n * heads + h reads kv head h / (heads / kv_heads) of its sample (consecutive query heads share
+// one: HuggingFace's repeat_kv order).  kv_heads == heads, or heads == 0: dense_view itself, behind
+// a uniform branch -- every launch without groups skips the two divisions below.
+__device__ __forceinline__ DenseView kv_view(int b, int S, int E, int heads, int kv_heads) {
+    if (heads <= 0 || kv_heads == heads) return dense_view(b, S, E, heads);
+    DenseView v;
+    const int n = b / heads, h = b - n * heads;
+    v.base = ((size_t)n * S * kv_heads + h / (heads / kv_heads)) * E;
+    v.ld = kv_heads * E;
+    return v;
+}
+
 // Copy S rows of E floats (row stride ld) into a packed [S][E] LDS tile; four independent
 // 16-byte loads per thread in flight.
 __device__ __forceinline__ void stage_rows(float *__restrict__ lds_dst,

@@ -35,6 +35,7 @@ _PROTOTYPES = {
     'spt_cdist_backward_workspace_bytes': ([_c_int] * 4, ctypes.c_int64),
     'spt_cdist_backward': ([_c_ptr] * 6 + [_c_int] * 4 + [_c_ptr], _c_int),
     'spt_lookup_forward': ([_c_ptr] * 3 + [_c_int] * 4 + [_c_ptr], _c_int),
+    'spt_lookup_forward_kv': ([_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr], _c_int),
     'spt_pq_encode_heads': ([_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr], _c_int),
     'spt_pq_encode_heads_bf16': ([_c_ptr] * 3 + [_c_int] * 6 + [_c_ptr], _c_int),
     'spt_pq_loss_workspace_bytes': ([ctypes.c_int64] + [_c_int] * 3, ctypes.c_int64),
@@ -68,6 +69,11 @@ _PROTOTYPES = {
                                    [_c_f32, _c_f32, _c_int, _c_int, _c_ptr], _c_int),
     'spt_attention_mfma_backward': ([_c_ptr, _c_int] + [_c_ptr] * 11 + [_c_int] * 4 +
                                     [_c_f32, _c_f32, _c_int, _c_int, _c_ptr], _c_int),
+    'spt_attention_mfma_forward_kv': ([_c_ptr, _c_int] + [_c_ptr] * 6 + [_c_int] * 4 +
+                                      [_c_f32, _c_f32, _c_int, _c_int, _c_int, _c_ptr], _c_int),
+    'spt_attention_mfma_backward_kv': ([_c_ptr, _c_int] + [_c_ptr] * 11 + [_c_int] * 4 +
+                                       [_c_f32, _c_f32, _c_int, _c_int, _c_int, _c_ptr], _c_int),
+    'spt_head_group_sum': ([_c_ptr, _c_ptr, ctypes.c_longlong] + [_c_int] * 3 + [_c_ptr], _c_int),
     'spt_attention_mfma_forward_bf16': ([_c_ptr, _c_int] + [_c_ptr] * 6 + [_c_int] * 4 +
                                         [_c_f32, _c_f32, _c_int, _c_int, _c_ptr], _c_int),
     'spt_attention_mfma_backward_bf16': ([_c_ptr, _c_int] + [_c_ptr] * 11 + [_c_int] * 4 +
@@ -500,13 +506,23 @@ def cdist_backward_cuda(query: torch.Tensor, table: torch.Tensor,
 
 
 def lookup_forward_cuda(config: torch.Tensor, query: torch.Tensor,
-                        key: torch.Tensor) -> torch.Tensor:
-    """extension/lookup.cu:87-174; ``config.size(0)`` is the sparsity coefficient."""
+                        key: torch.Tensor, kv_group: int = 1) -> torch.Tensor:
+    """extension/lookup.cu:87-174; ``config.size(0)`` is the sparsity coefficient.
+
+    ``kv_group`` g > 1 (grouped key/value heads): query ``[N * H, S, M]``, key ``[N * H / g, S, M]``,
+    and slice ``n * H + h`` matches against the key codes of slice ``n * (H / g) + h // g``
+    (``spt_lookup_forward_kv``): the output of the plain call on the key codes repeated per group."""
     _check_dim(key, 3, 'key')
     _check_dim(query, 3, 'query')
     _check_type(key, torch.int32, 'key')
     _check_type(query, torch.int32, 'query')
-    _require(query.shape == key.shape, 'query.sizes() == key.sizes()')
+    kv_group = int(kv_group)
+    if kv_group == 1:
+        _require(query.shape == key.shape, 'query.sizes() == key.sizes()')
+    else:
+        _require(kv_group > 1 and query.size(0) == key.size(0) * kv_group and query.shape[1:] == key.shape[1:],
+                 'query [N * H, S, M], key [N * H / kv_group, S, M]')
+        _require(query.is_contiguous() and key.is_contiguous(), 'contiguous codes')
     dev = _same_device(query, key)
     sparsity = int(config.size(0))
     B, S, M = query.shape
@@ -517,10 +533,18 @@ def lookup_forward_cuda(config: torch.Tensor, query: torch.Tensor,
     lib = load_library()
     with _on(dev):
         output = torch.empty([B, S, Z], dtype=torch.int32, device=dev)
-        rc = lib.spt_lookup_forward(
-            query.data_ptr(), key.data_ptr(), output.data_ptr(),
-            B, S, M, sparsity, _stream(dev)
-        )
+        if kv_group == 1:
+            rc = lib.spt_lookup_forward(
+                query.data_ptr(), key.data_ptr(), output.data_ptr(),
+                B, S, M, sparsity, _stream(dev)
+            )
+        else:
+            # (the samples' boundaries do not matter to the mapping: b // g is n * (H / g) + h // g for
+            # any H that g divides, so the batch is passed as one sample of B heads)
+            rc = lib.spt_lookup_forward_kv(
+                query.data_ptr(), key.data_ptr(), output.data_ptr(),
+                B, S, M, sparsity, B, B // kv_group, _stream(dev)
+            )
     if rc != 0:
         _raise(lib, rc, 'lookup_forward_cuda')
     return output
@@ -807,6 +831,9 @@ TILES_FULL, TILES_COMPACT = 0, 1
 # (tests) False: the backward decides the clamp's gradient mask on its split-bf16 scores -- the
 # behaviour before ABI 39, kept switchable so that a test can show what the exact mask changes
 EXACT_CLAMP = True
+# (tests) a list: attention_mfma_backward with grouped key/value heads appends its per-query-head
+# partials [2, N, S, H, E] (grad_k's, grad_v's) -- the operands of the fixed-order group sum
+GROUP_PARTS = None
 
 
 def attention_mfma_prepare(indices: torch.Tensor, seq_length: int,
@@ -840,8 +867,21 @@ def _bounds_behind(row_sum: torch.Tensor, B: int, S: int, n_bounds: int) -> int:
     return row_sum.data_ptr() + 4 * B * S if have >= 4 * (B * S + n_bounds) else 0
 
 
+def _kv_heads_of(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, kv_heads) -> int:
+    """Checks the shapes of an attention_mfma_* call; the kv head count (== H: not grouped)."""
+    N, S, H, E = q.shape
+    kv_heads = int(kv_heads)
+    if kv_heads == H:
+        _require(q.shape == k.shape == v.shape, 'q, k, v: same shape')
+        return H
+    _require(kv_heads > 0 and H % kv_heads == 0, 'kv_heads must divide the query heads')
+    _require(q.dtype == torch.float32, 'grouped key/value heads: float32 only')
+    _require(tuple(k.shape) == (N, S, kv_heads, E) and k.shape == v.shape, 'k, v: [N, S, kv_heads, E]')
+    return kv_heads
+
+
 def attention_mfma_forward(tiles, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                           scale: float, clamp: float, y_transposed: bool = False):
+                           scale: float, clamp: float, y_transposed: bool = False, kv_heads=None):
     """The attention core on the matrix cores (``spt_attention_mfma_forward``).
 
     q, k, v: ``[N, S, H, E]``; ``tiles``: :func:`attention_mfma_prepare` of the ``[N*H, nnz]``
@@ -852,11 +892,19 @@ def attention_mfma_forward(tiles, q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     ``row_sum`` is a view of the first ``N*H*S`` floats of a slightly longer buffer: behind them
     lie the forward's bounds on the row norms of q and k (``spt_attention_mfma_bounds_floats``),
     with which :func:`attention_mfma_backward` decides the clamp's gradient mask exactly.  Hand the
-    SAME tensor (or one sharing its storage: ``save_for_backward`` does) to the backward."""
+    SAME tensor (or one sharing its storage: ``save_for_backward`` does) to the backward.
+
+    ``kv_heads`` (grouped key/value heads, fp32): k, v ``[N, S, kv_heads, E]``; query head h reads kv
+    head ``h // (H // kv_heads)`` (``spt_attention_mfma_forward_kv``).  Same bits as the plain call
+    on ``k.repeat_interleave(H // kv_heads, dim=2)``; absent or equal to H it IS the plain call."""
     _check_dim(q, 4, 'q')
     _require(q.dtype in (torch.float32, torch.bfloat16), 'q: float32 or bfloat16 (bf16 storage)')
     _require(q.dtype == k.dtype == v.dtype, 'q, k, v: same dtype')
-    _require(q.shape == k.shape == v.shape, 'q, k, v: same shape')
+    if kv_heads is None:
+        _require(q.shape == k.shape == v.shape, 'q, k, v: same shape')
+        kv_heads = q.size(2)
+    else:
+        kv_heads = _kv_heads_of(q, k, v, kv_heads)
     _require(q.is_contiguous() and k.is_contiguous() and v.is_contiguous(), 'contiguous operands')
     N, S, H, E = q.shape
     B = N * H
@@ -873,10 +921,17 @@ def attention_mfma_forward(tiles, q: torch.Tensor, k: torch.Tensor, v: torch.Ten
         row_sum = stats[:B * S].view(B, S)
         fn = (lib.spt_attention_mfma_forward if q.dtype == torch.float32
               else lib.spt_attention_mfma_forward_bf16)
-        rc = fn(
-            tiles.buffer.data_ptr(), tiles.layout, q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(),
-            row_sum.data_ptr(), (row_sum.data_ptr() + 4 * B * S) if EXACT_CLAMP else 0, B, S, E, tiles.nnz, float(scale),
-            float(clamp), H, int(bool(y_transposed)), _stream(dev))
+        bounds = (row_sum.data_ptr() + 4 * B * S) if EXACT_CLAMP else 0
+        if kv_heads != H:
+            rc = lib.spt_attention_mfma_forward_kv(
+                tiles.buffer.data_ptr(), tiles.layout, q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(),
+                row_sum.data_ptr(), bounds, B, S, E, tiles.nnz, float(scale),
+                float(clamp), H, kv_heads, int(bool(y_transposed)), _stream(dev))
+        else:
+            rc = fn(
+                tiles.buffer.data_ptr(), tiles.layout, q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(),
+                row_sum.data_ptr(), bounds, B, S, E, tiles.nnz, float(scale),
+                float(clamp), H, int(bool(y_transposed)), _stream(dev))
     if rc != 0:
         _raise(lib, rc, 'attention_mfma_forward')
     return y, row_sum
@@ -884,7 +939,7 @@ def attention_mfma_forward(tiles, q: torch.Tensor, k: torch.Tensor, v: torch.Ten
 
 def attention_mfma_backward(tiles: MfmaTiles, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             y: torch.Tensor, grad_y: torch.Tensor, row_sum: torch.Tensor,
-                            scale: float, clamp: float, transposed: bool = False):
+                            scale: float, clamp: float, transposed: bool = False, kv_heads=None):
     """Backward of :func:`attention_mfma_forward` (``spt_attention_mfma_backward``).
 
     y, grad_y: the forward's output and its gradient, ``[N*H, S, E]`` or (``transposed``)
@@ -894,12 +949,22 @@ def attention_mfma_backward(tiles: MfmaTiles, q: torch.Tensor, k: torch.Tensor, 
 
     ``row_sum``: the tensor the forward returned for the same q, k (see there: the norm bounds
     behind it make the clamp's gradient mask that of the fp32 scores; ``EXACT_CLAMP = False``, or
-    a ``row_sum`` without them, leaves the mask to the split-bf16 scores)."""
+    a ``row_sum`` without them, leaves the mask to the split-bf16 scores).
+
+    ``kv_heads`` (grouped key/value heads, fp32; k, v ``[N, S, kv_heads, E]``): returns grad_q
+    ``[N, S, H, E]`` and grad_k, grad_v ``[N, S, kv_heads, E]`` (two views of one buffer).  The
+    key-owned kernel writes one partial per query head -- the bits of the plain call on repeated
+    k, v -- into a buffer this call owns, and ``spt_head_group_sum`` adds each group's partials in
+    ascending head order: deterministic, no atomics."""
     _check_dim(q, 4, 'q')
     _require(q.dtype in (torch.float32, torch.bfloat16), 'q: float32 or bfloat16 (bf16 storage)')
     _require(q.dtype == k.dtype == v.dtype == y.dtype == grad_y.dtype, 'q, k, v, y, grad_y: same dtype')
     _check_type(row_sum, torch.float32, 'row_sum')
-    _require(q.shape == k.shape == v.shape, 'q, k, v: same shape')
+    if kv_heads is None:
+        _require(q.shape == k.shape == v.shape, 'q, k, v: same shape')
+        kv_heads = q.size(2)
+    else:
+        kv_heads = _kv_heads_of(q, k, v, kv_heads)
     for t in (q, k, v, y, grad_y, row_sum):
         _require(t.is_contiguous(), 'contiguous operands')
     N, S, H, E = q.shape
@@ -909,6 +974,27 @@ def attention_mfma_backward(tiles: MfmaTiles, q: torch.Tensor, k: torch.Tensor, 
     _require(row_sum.numel() == B * S, 'row_sum: [N * H, S]')
     dev = _same_device(tiles.buffer, q, k, v, y, grad_y, row_sum)
     lib = load_library()
+    if kv_heads != H:
+        with _on(dev):
+            grad_q = torch.empty_like(q)
+            parts = torch.empty([2, N, S, H, E], dtype=torch.float32, device=dev)
+            grad_kv = torch.empty([2, N, S, kv_heads, E], dtype=torch.float32, device=dev)
+            delta = torch.empty([2, B, S], dtype=torch.float32, device=dev)
+            bounds = _bounds_behind(row_sum, B, S, lib.spt_attention_mfma_bounds_floats(B)) if EXACT_CLAMP else 0
+            rc = lib.spt_attention_mfma_backward_kv(
+                tiles.buffer.data_ptr(), tiles.layout, q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(),
+                grad_y.data_ptr(), row_sum.data_ptr(), bounds, delta.data_ptr(), grad_q.data_ptr(),
+                parts[0].data_ptr(), parts[1].data_ptr(), B, S, E, tiles.nnz, float(scale), float(clamp),
+                H, kv_heads, int(bool(transposed)), _stream(dev))
+            if rc == 0:
+                # both gradients' partials in one launch: [2 * N * S] rows of H heads
+                rc = lib.spt_head_group_sum(parts.data_ptr(), grad_kv.data_ptr(), 2 * N * S, H, kv_heads, E,
+                                            _stream(dev))
+        if rc != 0:
+            _raise(lib, rc, 'attention_mfma_backward')
+        if GROUP_PARTS is not None:
+            GROUP_PARTS.append(parts)
+        return grad_q, grad_kv[0], grad_kv[1]
     with _on(dev):
         # (one buffer: the projections' backward contracts the three as ONE matrix product when
         # they are equally spaced in memory -- layers/tuning/lora.py, `qkv_dx`)

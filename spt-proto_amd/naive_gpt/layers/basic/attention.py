@@ -12,6 +12,20 @@ from torch import nn
 from naive_gpt import layers
 
 
+def expand_kv(q: torch.Tensor, *kv):
+    """Grouped key/value heads in front of code written for one K/V head per query head: k, v
+    ``[N, S, kv_heads, E]`` repeated per group along the head axis (kv head j serves query heads
+    j g .. j g + g - 1, HuggingFace's repeat_kv order).  Equal head counts: the tensors themselves."""
+    heads = q.size(2)
+    out = []
+    for t in kv:
+        if t.size(2) != heads:
+            assert heads % t.size(2) == 0, 'kv heads {} must divide query heads {}'.format(t.size(2), heads)
+            t = t.repeat_interleave(heads // t.size(2), dim=2)
+        out.append(t)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 class VanillaAttention(nn.Module):
     def __init__(self, d_head: int, p_dropout: float):
         super().__init__()
@@ -33,19 +47,29 @@ class VanillaAttention(nn.Module):
         y = torch.einsum('naij, njae -> niae', attn, v)
         return y.contiguous()
 
+    def _forward_grouped(self, q, k, v, attn_mask):
+        """Grouped key/value heads: the dense cores repeat k and v in front of the code below (the V2
+        sparse layers override this: their kernels read the kv head in place)."""
+        k, v = expand_kv(q, k, v)
+        return VanillaAttention.forward(self, q, k, v, attn_mask=attn_mask)
+
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                 attn_mask: torch.Tensor = None):
         assert q.dim() == 4 and k.dim() == 4 and v.dim() == 4
         assert q.size(0) == k.size(0) == v.size(0)
+        if k.size(2) != q.size(2):
+            return self._forward_grouped(q, k, v, attn_mask)
         attn = self._get_attn(q=q, k=k, attn_mask=attn_mask)
         return self._apply_attn(attn, v=v)
 
 
 class RotaryAttention(VanillaAttention):
-    def __init__(self, d_head: int, p_dropout: float, max_length: int = 2048):
+    def __init__(self, d_head: int, p_dropout: float, max_length: int = 2048,
+                 rope_base: float = 10000.0):
         super().__init__(d_head=d_head, p_dropout=p_dropout)
+        self.rope_base = float(rope_base)       # (HuggingFace's rope_theta; LLaMA-3: 500000)
         self.embedding = layers.RotaryEmbedding(
-            n_embeddings=max_length, d_model=d_head
+            n_embeddings=max_length, d_model=d_head, base=self.rope_base
         )
         self.cached_ids: torch.Tensor
         self.register_buffer('cached_ids', torch.arange(max_length))

@@ -10,19 +10,23 @@ import torch
 from torch import nn
 
 from . import fused_norm
-from .multihead import project_heads
+from .multihead import kv_heads_of, project_heads
 from ..tuning import recompute
 
 
 class MultiheadAttention(nn.Module):
-    def __init__(self, d_model: int, n_heads: int, attention_fn: nn.Module, bias: bool):
+    def __init__(self, d_model: int, n_heads: int, attention_fn: nn.Module, bias: bool,
+                 n_kv_heads: int = None):
         super().__init__()
         self.d_model = d_model
         self.n_heads = n_heads
+        # grouped key/value heads (GQA / MQA): kv head j serves query heads j g .. j g + g - 1
+        self.n_kv_heads = kv_heads_of(d_model, n_heads, n_kv_heads)
+        d_kv = self.n_kv_heads * (d_model // n_heads)
         self.attn_fn = attention_fn
         self.linear_q = nn.Linear(d_model, d_model, bias=bias)
-        self.linear_k = nn.Linear(d_model, d_model, bias=bias)
-        self.linear_v = nn.Linear(d_model, d_model, bias=bias)
+        self.linear_k = nn.Linear(d_model, d_kv, bias=bias)
+        self.linear_v = nn.Linear(d_model, d_kv, bias=bias)
         self.linear_o = nn.Linear(d_model, d_model, bias=bias)
 
     def forward(self, q, k, v, attn_mask: torch.Tensor = None):
@@ -32,12 +36,12 @@ class MultiheadAttention(nn.Module):
 class TransformerBlock(nn.Module):
     def __init__(self, d_model: int, n_heads: int, layernorm_fn: nn.Module,
                  attention_fn: nn.Module, feedforward_fn: nn.Module,
-                 attention_bias: bool, pre_norm: bool):
+                 attention_bias: bool, pre_norm: bool, n_kv_heads: int = None):
         super().__init__()
         self.pre_norm = pre_norm
         self.mha = MultiheadAttention(
             d_model=d_model, n_heads=n_heads,
-            attention_fn=attention_fn, bias=attention_bias
+            attention_fn=attention_fn, bias=attention_bias, n_kv_heads=n_kv_heads
         )
         self.ffd = copy.deepcopy(feedforward_fn)
         self.norm1 = copy.deepcopy(layernorm_fn)

@@ -24,6 +24,7 @@ import os
 import torch
 
 from naive_gpt import ext, kernels, layers
+from naive_gpt.layers.basic.attention import expand_kv
 
 SPARSE_COEFF = 8     # Z = S / 8 keys per query (reference: attention.py:109-117)
 CLAMP = 10.0         # reference: attention.py:125-127
@@ -34,6 +35,13 @@ FOLD_PQ_LOSS = True
 PAIR_PQ_LOSS = os.environ.get('SPT_PQ_PAIR', '1') != '0'
 # SparseRotaryAttentionV2: the rotary embedding of q and k as one launch (spt_rotary)
 ROTARY_KERNEL = os.environ.get('SPT_ROTARY_KERNEL', '1') != '0'
+
+
+def gqa_expand_forced() -> bool:
+    """SPT_GQA_EXPAND=1: grouped key/value heads (k, v [N, S, kv_heads, E]) are repeated per group in
+    front of the one-K/V-head-per-query-head code on the GPU as well -- the A/B partner of the kernels
+    that read the kv head in place (read per call: tests flip it)."""
+    return os.environ.get('SPT_GQA_EXPAND', '0') == '1'
 
 
 class _ScaledClampedSDDMM(torch.autograd.Function):
@@ -176,7 +184,11 @@ class _MfmaAttention(torch.autograd.Function):
         # `indices` come straight from kernels.lookup: only its padding column 0 repeats in a
         # row, which is what the compact tile layout needs (70 -> 17 MB per BERT-large layer)
         tiles = ext.attention_mfma_prepare(indices, q.size(1), lookup_pattern=True)
-        y, row_sum = ext.attention_mfma_forward(tiles, q, k, v, scale, CLAMP, y_transposed=True)
+        # grouped key/value heads (k, v [N, S, kv_heads, E]): the kernels read the kv head of each
+        # query head in place and grad_k / grad_v come back reduced over each group
+        ctx.kv_heads = None if k.size(2) == q.size(2) else k.size(2)
+        y, row_sum = ext.attention_mfma_forward(tiles, q, k, v, scale, CLAMP, y_transposed=True,
+                                                kv_heads=ctx.kv_heads)
         ctx.scale, ctx.tiles = scale, tiles
         if ctx.armed:
             ctx.save_for_backward(q, k, v, y, row_sum, table)
@@ -190,7 +202,7 @@ class _MfmaAttention(torch.autograd.Function):
         q, k, v, y, row_sum = ctx.saved_tensors[:5]
         grad_q, grad_k, grad_v = ext.attention_mfma_backward(
             ctx.tiles, q, k, v, y, grad_out.contiguous(), row_sum, ctx.scale, CLAMP,
-            transposed=True)
+            transposed=True, kv_heads=ctx.kv_heads)
         if not ctx.armed:
             return None, grad_q, grad_k, grad_v, None
         table = ctx.saved_tensors[5]
@@ -325,7 +337,9 @@ class _SparseCore:
                 and ext.head_layout_supported(s, e, n * h))
 
     def _sparse_attn_heads(self, q: torch.Tensor, k: torch.Tensor):
-        """MI355X fast path: no layout copies (see module docstring)."""
+        """MI355X fast path: no layout copies (see module docstring).  k may hold fewer heads than q
+        (grouped key/value heads, matrix-core shapes only: `_sparse_attn` decides): it is encoded
+        and read un-expanded."""
         seq_length, heads = q.size(1), q.size(2)
         q, k = q.contiguous(), k.contiguous()
         q_c = k_c = None
@@ -364,6 +378,11 @@ class _SparseCore:
             q_c = ext.pq_encode_heads(q.detach(), table)
         if k_c is None:
             k_c = ext.pq_encode_heads(k.detach(), table)
+        if k.size(2) != heads:          # grouped key/value heads: `_sparse_attn` sends matrix-core shapes only
+            assert mfma
+            topk_indices = kernels.lookup(q_c, k_c, sparse_coeff=SPARSE_COEFF, kv_group=heads // k.size(2))
+            ext.note_path('attention', 'mfma_gqa')
+            return 'mfma', self._uniform_indptr(seq_length, q.device), topk_indices.flatten(start_dim=1), q, k
         topk_indices = kernels.lookup(q_c, k_c, sparse_coeff=SPARSE_COEFF)
         csr_indices = topk_indices.flatten(start_dim=1)
         indptr = self._uniform_indptr(seq_length, q.device)
@@ -383,6 +402,26 @@ class _SparseCore:
 
     def _sparse_attn(self, q: torch.Tensor, k: torch.Tensor):
         # q, k: [N, S, H, E] -> [N*H, S, E]
+        if k.size(2) != q.size(2):
+            # grouped key/value heads: the matrix-core kernels read the kv head in place; every other
+            # path gets k (and, in _sparse_forward, v) repeated per group
+            assert q.size(2) % k.size(2) == 0 and q.shape[:2] == k.shape[:2] and q.size(3) == k.size(3)
+            forced = gqa_expand_forced()
+            if not forced and q.dtype == torch.float32 and self.quantizer.method == 'v2' and self._mfma_ok(q):
+                return self._sparse_attn_heads(q, k)
+            ext.note_path('attention', 'gqa_expanded', fallback=True,
+                          why=lambda: 'q {} k {} {}: {}'.format(
+                              tuple(q.shape), tuple(k.shape), q.dtype,
+                              'SPT_GQA_EXPAND=1' if forced else
+                              'grouped key/value heads are read in place by the fp32 matrix-core kernels only '
+                              '(cuda, PQ v2, n * h >= 32, d_head 64 / 80 / 128, S <= 2048)'))
+            if self._take_trigger():
+                # the PQ loss of q and of the UN-expanded k, whichever form computes the attention
+                self.__dict__.pop('_armed_losses', None)
+                loss_q = self.quantizer.train_loss_and_codes(q.float().contiguous())[0]
+                loss_k = self.quantizer.train_loss_and_codes(k.float().contiguous())[0]
+                self.register_buffer('loss', loss_q + loss_k, persistent=False)
+            k = expand_kv(q, k)
         assert q.size() == k.size()
         if self._head_layout_ok(q) and self.quantizer.method == 'v2':
             return self._sparse_attn_heads(q, k)
@@ -409,6 +448,14 @@ class _SparseCore:
         values = _ScaledClampedSDDMM.apply(indptr, csr_indices, q, k, self.scaling)
         values = kernels.softmax(indptr, csr_indices, values=values)
         return indptr, csr_indices, values
+
+    def _sparse_forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        """_sparse_attn + _sparse_apply; with grouped key/value heads v follows k: left as it is when
+        the attention kept k's heads (the matrix-core kernels), repeated per group otherwise."""
+        attn = self._sparse_attn(q, k)
+        if not (len(attn) == 5 and attn[0] == 'mfma' and attn[4].size(2) == v.size(2)):
+            v = expand_kv(q, v)
+        return self._sparse_apply(attn, v)
 
     def _sparse_apply(self, attn, v: torch.Tensor):
         v_size = v.size()
@@ -491,11 +538,14 @@ class SparseVanillaAttentionV2(layers.VanillaAttention, _SparseCore):
     def _apply_attn(self, attn, v):
         return self._sparse_apply(attn, v)
 
+    def _forward_grouped(self, q, k, v, attn_mask):
+        return self._sparse_forward(q, k, v)
+
 
 class SparseRotaryAttentionV1(layers.RotaryAttention):
     def __init__(self, d_head: int, p_dropout: float, d_codeword: int,
-                 n_codewords: int, n_subspaces: int):
-        super().__init__(d_head=d_head, p_dropout=p_dropout)
+                 n_codewords: int, n_subspaces: int, rope_base: float = 10000.0):
+        super().__init__(d_head=d_head, p_dropout=p_dropout, rope_base=rope_base)
         self.d_codeword = d_codeword
         self.n_codewords = n_codewords
         self.n_subspaces = n_subspaces
@@ -513,8 +563,9 @@ class SparseRotaryAttentionV1(layers.RotaryAttention):
 
 
 class SparseRotaryAttentionV2(layers.RotaryAttention, _SparseCore):
-    def __init__(self, d_head: int, p_dropout: float, d_codeword: int, n_codewords: int):
-        layers.RotaryAttention.__init__(self, d_head=d_head, p_dropout=p_dropout)
+    def __init__(self, d_head: int, p_dropout: float, d_codeword: int, n_codewords: int,
+                 rope_base: float = 10000.0):
+        layers.RotaryAttention.__init__(self, d_head=d_head, p_dropout=p_dropout, rope_base=rope_base)
         self.quantizer = layers.PQV2(d_codeword=d_codeword, n_codewords=n_codewords,
                                      n_subspaces=d_head // d_codeword)
         _make_trigger(self)
@@ -524,7 +575,7 @@ class SparseRotaryAttentionV2(layers.RotaryAttention, _SparseCore):
         assert isinstance(source, SparseRotaryAttentionV1)
         model = layers.SparseRotaryAttentionV2(
             d_head=source.d_head, d_codeword=source.d_codeword,
-            n_codewords=source.n_codewords, p_dropout=0.0
+            n_codewords=source.n_codewords, p_dropout=0.0, rope_base=source.rope_base
         )
         report = model.load_state_dict(source.state_dict(), strict=False)
         if len(report.missing_keys) != 0:
@@ -547,9 +598,30 @@ class SparseRotaryAttentionV2(layers.RotaryAttention, _SparseCore):
             ext.note_path('rotary', 'kernel')
             q, k, v = _Rotary3.apply(q, k, v, cos, sin)
             return self._apply_attn(self._sparse_attn(q, k), v)
+        if ROTARY_KERNEL and q.shape != k.shape and k.shape == v.shape \
+                and ext.rotary_supported(q, cos, sin) and ext.rotary_supported(k, cos, sin):
+            # grouped key/value heads: q and k differ in shape, one launch each; v is untouched
+            ext.note_path('rotary', 'kernel')
+            return self._sparse_forward(_Rotary1.apply(q, cos, sin), _Rotary1.apply(k, cos, sin), v)
         ext.note_path('rotary', 'torch', fallback=q.is_cuda,
                       why=lambda: 'q {} {}'.format(tuple(q.shape), q.dtype))
+        if k.size(2) != q.size(2):
+            return self._sparse_forward(self._rotate(q), self._rotate(k), v)
         return super().forward(q, k, v, attn_mask=attn_mask)
+
+
+class _Rotary1(torch.autograd.Function):
+    """rotary(x) of one tensor (spt_rotary): q or k of grouped key/value heads, whose shapes differ."""
+
+    @staticmethod
+    def forward(ctx, x, cos, sin):
+        ctx.save_for_backward(cos, sin)
+        return ext.rotary([x], 1, cos, sin)[0]
+
+    @staticmethod
+    def backward(ctx, dx):
+        cos, sin = ctx.saved_tensors
+        return ext.rotary([dx.contiguous()], 1, cos, sin, transpose=True)[0], None, None
 
 
 class _Rotary3(torch.autograd.Function):

@@ -73,9 +73,11 @@ class SparseLoRAHandler(LoRAHandler):
         return LoRAHandler.onEmbedding(self, name=name, child=child)
 
     def _to_v1(self, cls, name: str, child: nn.Module):
+        # (a rotary attention keeps its base: LLaMA-3's rope_theta is not the default)
+        extra = {'rope_base': child.rope_base} if hasattr(child, 'rope_base') else {}
         new_model = cls(d_head=child.d_head, p_dropout=child.p_dropout,
                         d_codeword=D_CODEWORD, n_codewords=N_CODEWORDS,
-                        n_subspaces=child.d_head // D_CODEWORD)
+                        n_subspaces=child.d_head // D_CODEWORD, **extra)
         _log('[UPGRADE]', name, child, new_model)
         return new_model
 

@@ -22,6 +22,12 @@ from naive_gpt import models
 
 CONFIG_KEYS = ('d_model', 'n_heads', 'n_layers', 'vocab_size', 'd_feedforward',
                'max_length', 'p_dropout')
+# Optional keys (LLaMA family): key -> the value that a config WITHOUT the key means.  A config
+# holds one only when it differs from that value, so every file written before they existed, and
+# every file of a model that does not need them, has exactly CONFIG_KEYS.
+#   n_kv_heads  grouped-query attention: fewer key/value heads than query heads (None: n_heads)
+#   rope_theta  the rotary embedding's base (LLaMA-3: 500000)
+OPTIONAL_KEYS = {'n_kv_heads': None, 'rope_theta': 10000.0}
 
 
 def model_family(path_or_name: str) -> str:
@@ -38,7 +44,14 @@ def build_model(family: str, config: dict) -> nn.Module:
     if missing:
         raise KeyError('checkpoint config lacks ' + ', '.join(missing))
     cls = {'opt': models.OPTModel, 'llama': models.LLaMAModel}[family]
-    return cls(**{k: config[k] for k in CONFIG_KEYS})
+    kwargs = {k: config[k] for k in CONFIG_KEYS}
+    extra = {k: config[k] for k in OPTIONAL_KEYS if k in config}
+    if extra.get('n_kv_heads') == config['n_heads']:
+        del extra['n_kv_heads']
+    if extra and family != 'llama':
+        raise KeyError('checkpoint config keys {} belong to the llama family, not to {}'.format(
+            sorted(extra), family))
+    return cls(**kwargs, **extra)
 
 
 def save_checkpoint(path: str, config: dict, model: nn.Module) -> None:
@@ -177,12 +190,23 @@ def llama_state_from_hf(hf_state: Dict[str, torch.Tensor]) -> Dict[str, torch.Te
 def config_from_hf(hf_config) -> dict:
     """``script/1-convert.py:146-160``."""
     d_ff = getattr(hf_config, 'ffn_dim', None) or hf_config.intermediate_size
-    return {
+    config = {
         'd_model': hf_config.hidden_size, 'n_heads': hf_config.num_attention_heads,
         'n_layers': hf_config.num_hidden_layers, 'vocab_size': hf_config.vocab_size,
         'd_feedforward': d_ff, 'max_length': hf_config.max_position_embeddings,
         'p_dropout': 0.0,
     }
+    # grouped-query checkpoints (TinyLlama, Mistral, LLaMA-3) and a rotary base other than 10000:
+    # written only when they differ from what their absence means (OPTIONAL_KEYS)
+    n_kv_heads = getattr(hf_config, 'num_key_value_heads', None)
+    if n_kv_heads is not None and int(n_kv_heads) != int(config['n_heads']):
+        config['n_kv_heads'] = int(n_kv_heads)
+    rope_theta = getattr(hf_config, 'rope_theta', None)
+    if rope_theta is None:      # (newer transformers keep the base in the config's rope parameters)
+        rope_theta = (getattr(hf_config, 'rope_parameters', None) or {}).get('rope_theta')
+    if rope_theta is not None and float(rope_theta) != OPTIONAL_KEYS['rope_theta']:
+        config['rope_theta'] = float(rope_theta)
+    return config
 
 
 def load_hf_state(model: nn.Module, family: str, hf_state: Dict[str, torch.Tensor]) -> None:
